@@ -15,8 +15,8 @@ finite timeout (``pg_kwargs``).  Modes:
 * ``--mode param-range`` (default; SURVEY.md §8(e) primary, bit-exact): every rank reduces its own
   parameter range of all K clients -- no data-path collective.  ``--scaling weak`` (default): each
   rank owns a full M-param slice of an N*M-param model; ``--scaling strong``: the workload's own M
-  is split over the N ranks (C3 at 64 x 125M over 8 GPUs = 15.6M params per GPU).  With N > 1 and
-  one GPU per rank the SAME line also carries ``client_shard``: the north-star client-sharded
+  is split over the N ranks (C3 at 64 x 125M over 8 GPUs = 15.6M params per GPU).  With ``--full``, N > 1
+  and one GPU per rank the SAME line also carries ``client_shard``: the north-star client-sharded
   mode timed right after, weak (every rank holds the workload's K clients, N*K in all), combine
   ``--combine`` (default striped) -- step time, block-kernel time, exchange time, GB/s, fraction
   of N x 8 TB/s, and weak efficiency against the parameter-range kernel time of one GPU -- and
@@ -29,6 +29,15 @@ finite timeout (``pg_kwargs``).  Modes:
 * ``--engine multi-device``: the drop-in's own multi-GPU path, ONE process driving N GPUs
   (MultiDeviceEngine: host buckets staged over each GPU's PCIe link, per-shard kernel time from
   HIP events on the session streams) -- an end-to-end line, not the device-resident metric.
+
+A plain run (``--gpus 1 --steps N --warmup W``) does what the headline figure needs and no more:
+it sets up the buckets, warms up, times exactly N steps, writes ``--dump-outputs DIR`` if asked and
+prints the line.  ``--full`` adds everything else to the same line: the kernel timed launch by
+launch (median / min), the parity spot check, the read-stream ceiling, the PMC traffic record, the
+CPU baseline and, at N > 1, the client-shard and multi-device legs; without it those fields are
+null.  ``--dump-outputs DIR`` writes the arrays the last timed step produced (``out``; Scaffold:
+``dout``, ``cout``) as ``DIR/<name>.npy``; the inputs are seeded, so two builds run with the same
+arguments can be compared file by file (``dump_outputs``).
 
 value = algorithmic bytes of the whole job / max-over-ranks time.  Algorithmic bytes (SURVEY.md
 §8(d)): FedAvg K*M*s_in + M*s_out; Scaffold 2*K*M*s_in + M*s_in + 2*M*8.
@@ -66,6 +75,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, also everything else the benchmark measures or checks: the "
+                         "kernel launch by launch, the parity spot check, the read-stream ceiling, the PMC traffic "
+                         "record, the CPU baseline and, at N > 1, the client-shard and multi-device legs "
+                         "(off: set-up, warm-up, the timed steps, the line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float32 / float64; an output too large for the 64 MB limit is written "
+                         "as a fixed, seeded sample of its elements)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--mode", default="param-range", choices=["param-range", "client-shard"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"])
@@ -211,6 +229,45 @@ def synth_tiled(torch, K, M, kind, device, seed0, tv):
 def lib_sha256() -> str:
     p = ROOT / "substrafl_amd" / "libfedagg.so"
     return hashlib.sha256(p.read_bytes()).hexdigest()[:16] if p.exists() else ""
+
+
+DUMP_BUDGET_BYTES = 48 << 20  # all arrays of one --dump-outputs call together (the limit is 64 MB)
+DUMP_SEED = 20241016
+
+
+def dump_outputs(dirname, arrays, rank=0):
+    """``--dump-outputs DIR``: write each (name, array, M) -- the first M elements of a device
+    tensor or host array the timed path produced in its last step -- as DIR/<name>.npy (ranks
+    above 0: DIR/<name>.rank<r>.npy), float32 or float64 as computed.  The arrays share
+    DUMP_BUDGET_BYTES; one that does not fit its share is written as the elements at
+    ``default_rng(DUMP_SEED).integers(0, M, n)`` sorted -- the same elements in every run and
+    build, so two dumps compare file by file.  Returns what was written, for the line."""
+    out_dir = Path(dirname)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    written = {}
+    for name, arr, M in arrays:
+        is_np = isinstance(arr, np.ndarray)
+        item = arr.itemsize if is_np else arr.element_size()
+        n = share // item
+        if M > n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, M, n))
+            if is_np:
+                host = arr[idx]
+            else:
+                import torch
+
+                host = arr[torch.from_numpy(idx).to(arr.device)].cpu().numpy()
+        else:
+            host = arr[:M] if is_np else arr[:M].cpu().numpy()
+        host = np.ascontiguousarray(host)
+        if host.dtype not in (np.float32, np.float64):
+            host = host.astype(np.float32)
+        fname = f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"
+        np.save(out_dir / fname, host)
+        written[fname] = {"dtype": str(host.dtype), "elements": int(host.size), "of": int(M),
+                          "sampled": bool(M > n)}
+    return written
 
 
 def read_traffic(args, sha):
@@ -506,14 +563,16 @@ def main():
         line = client_shard_line(args, ctx, cs)
     else:
         line, info = measure_param_range(args, ctx)
-        if (world > 1 and args.client_shard == "auto") or args.client_shard == "force":
+        # the legs beside the parameter-range value: with --full (auto, N > 1) or forced by name
+        if (world > 1 and args.client_shard == "auto" and args.full) or args.client_shard == "force":
             if own_gpus:  # the north-star mode beside it: client buckets sharded, exchanged over xGMI
                 line.update(client_shard_legs(args, ctx, info))
             else:
                 line["client_shard"] = {"skipped": f"needs one GPU per rank for RCCL ({world} ranks, {ndev} GPUs)"}
                 if args.client_shard == "force":  # the push leg needs no RCCL: rehearse it with ranks sharing GPUs
                     line.update(client_shard_legs(args, ctx, info, only_push=True))
-        if own_gpus and ((world > 1 and args.multi_device_leg == "auto") or args.multi_device_leg == "force"):
+        if own_gpus and ((world > 1 and args.multi_device_leg == "auto" and args.full)
+                         or args.multi_device_leg == "force"):
             line["multi_device"] = multi_device_leg(args, ctx)
     if rank == 0 and not args.client_shard_child:
         print(json.dumps(line), flush=True)
@@ -604,27 +663,34 @@ def measure_param_range(args, ctx):
 
     elapsed, ev_ms = _timed(ctx, step, args.steps, args.warmup)
     kern_ms = ev_ms / args.steps  # the step IS the one kernel, launched back to back
-    # the kernel alone, launch by launch (HIP events on its stream): median / min for the spread
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-           for _ in range(max(5, min(args.steps, 20)))]
-    for a, b in evs:
-        a.record(stream)
-        plan.launch(stream)
-        b.record(stream)
-    torch.cuda.synchronize(device)
-    each_ms = np.array([a.elapsed_time(b) for a, b in evs])
+    dumped = None
+    if args.dump_outputs:  # the last timed step's result, before anything else launches
+        outs = [("dout", dout, M), ("cout", cout, M)] if scaffold else [("out", out, M)]
+        dumped = dump_outputs(args.dump_outputs, outs, rank)
+    each_ms = None
+    if args.full:  # the kernel alone, launch by launch (HIP events on its stream): median / min for the spread
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+               for _ in range(max(5, min(args.steps, 20)))]
+        for a, b in evs:
+            a.record(stream)
+            plan.launch(stream)
+            b.record(stream)
+        torch.cuda.synchronize(device)
+        each_ms = np.array([a.elapsed_time(b) for a, b in evs])
     elapsed, kern_ms_max = ctx.max_over_ranks([elapsed, kern_ms])
     ms_per_step = elapsed / args.steps * 1e3
     value = bytes_job / (elapsed / args.steps) / 1e9
 
-    parity = spot_check(torch, world, rank, scaffold, K, M, layout, n_samples, kind, device, env)
-    read_ceiling = read_probe(torch, ctx.lib, env["clients"] if not scaffold else env["delta"], stream, device,
-                              ctx.native)
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline(wl, args.cpu_seconds, full=_cpu_full(args))
+    # --full only: the checks and the figures that take runs (or a host computation) of their own
+    parity, read_ceiling, cpu, traffic, tsrc = None, 0.0, None, None, None
     sha = lib_sha256()
-    traffic, tsrc = read_traffic(args, sha) if (world == 1 or args.scaling == "weak") else (None, None)
+    if args.full:
+        parity = spot_check(torch, world, rank, scaffold, K, M, layout, n_samples, kind, device, env)
+        read_ceiling = read_probe(torch, ctx.lib, env["clients"] if not scaffold else env["delta"], stream, device,
+                                  ctx.native)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline(wl, args.cpu_seconds, full=_cpu_full(args))
+        traffic, tsrc = read_traffic(args, sha) if (world == 1 or args.scaling == "weak") else (None, None)
     achieved = bytes_kernel / (kern_ms / 1e3) / 1e9 if kern_ms > 0 else 0.0
     if not scaffold:
         kname = f"fedavg_kernel<{'BF16' if kind == 'bf16' else 'F32'}>"
@@ -673,8 +739,8 @@ def measure_param_range(args, ctx):
             "kernel": kname,
             "kernel_ms": round(kern_ms, 5),
             "kernel_ms_max_over_ranks": round(kern_ms_max, 5),
-            "kernel_ms_median": round(float(np.median(each_ms)), 5),
-            "kernel_ms_min": round(float(each_ms.min()), 5),
+            "kernel_ms_median": round(float(np.median(each_ms)), 5) if each_ms is not None else None,
+            "kernel_ms_min": round(float(each_ms.min()), 5) if each_ms is not None else None,
             "kernel_timing": "HIP events on the launch stream: timed region / steps",
             "read_stream_ceiling_GBps": round(read_ceiling, 1) if read_ceiling > 0 else None,
             "frac_of_read_ceiling": round(achieved / read_ceiling, 4) if read_ceiling > 0 else None,
@@ -683,7 +749,10 @@ def measure_param_range(args, ctx):
         "parity": parity,
         "build": {"lib_sha256": sha},
         "device_quiet": getattr(ctx, "quiet", None),
+        "full": bool(args.full),  # false: the spread, parity, read-ceiling, traffic and cpu_baseline fields are null
     }
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if world > 1:
         line["process_group"] = {"backend": ctx.backend, "timeout_s": PG_TIMEOUT_S}
         # the job's fraction of N x 8 TB/s (the driver computes T(1)/T(N) itself)
@@ -1114,6 +1183,9 @@ def measure_client_shard(args, ctx, combine, scaling, t1_ms=None, t1_source=None
     steps = max(1, min(args.steps, args.client_shard_steps))
     warm = max(1, min(args.warmup, 5))
     elapsed, _ev = _timed(ctx, step, steps, warm)
+    dumped = None
+    if getattr(args, "dump_outputs", "") and variants and rank == 0:  # the root's result of the last timed step
+        dumped = dump_outputs(args.dump_outputs, [(k, v, M) for k, v in outs.items()])
     # the block kernels alone, back to back (HIP events on their stream)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     compute_only()
@@ -1175,6 +1247,8 @@ def measure_client_shard(args, ctx, combine, scaling, t1_ms=None, t1_source=None
         "output_checksum": checksum,
         "checksum_comparable": comparable,
     }
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     if getattr(tr, "push", False):
         res["late_landing_tags"] = int(sum(tr.late_tags()))  # every rank's count: one shared page
         res["wait_errors"] = tr.errors()
@@ -1751,6 +1825,7 @@ def multi_device_bench(args):
         shards.append(eng.last_timing["shards"])
     wall = float(np.median(walls))
     py_bits = np.concatenate([np.asarray(a).reshape(-1) for a in res]).view(np.uint32).copy()
+    dumped = dump_outputs(args.dump_outputs, [("out", py_bits.view(np.float32), M)]) if args.dump_outputs else None
     del res
     # the same plan through the one-call C entry (fedagg_multi_fedavg_f32, csrc/multi.hip): the
     # orchestration in C++ instead of Python threads, same devices, same host buckets
@@ -1798,6 +1873,7 @@ def multi_device_bench(args):
         "placement": eng.placement_report(),
         "native_c_entry": native_entry,
         "cpus_allowed": len(os.sched_getaffinity(0)),
+        "dumped_outputs": dumped,
         "note": "end-to-end (pinned-ring pack + H2D + kernel + D2H); not the device-resident metric",
     }), flush=True)
 
@@ -1847,6 +1923,7 @@ def rehearse(args, world, rank):
         x = x * np.float32(1.0)
     elapsed = time.perf_counter() - t0
     cs = gather_leg = None
+    with_legs = (args.client_shard == "auto" and args.full) or args.client_shard == "force"
     if world > 1:
         dist.barrier()
         t = torch.tensor([elapsed], dtype=torch.float64)
@@ -1857,7 +1934,7 @@ def rehearse(args, world, rank):
 
             ctx = _Ctx(torch=torch, dist=dist, world=world, rank=rank, device=types.SimpleNamespace(index=rank))
             legs = client_shard_legs(args, ctx, {"kern_ms": 1.0})
-        elif args.client_shard != "off":
+        elif with_legs:
             cs = _rehearse_client_shard(args, world, rank)
             probe = p2p_probe(torch, dist, rank, world, torch.device("cpu"), dist.barrier,
                               lambda v: [float(x) for x in _all_max(torch, dist, v)], ring_mib=1, peers_mib=1, iters=2)
@@ -1876,6 +1953,8 @@ def rehearse(args, world, rank):
             line["process_group"] = {"backend": dist.get_backend(), "timeout_s": PG_TIMEOUT_S}
             line.update(legs)
             line["line_wall_s"] = round(time.monotonic() - _T_START, 1)
+        elif world > 1 and not with_legs:  # no --full: the parameter-range line alone
+            line["process_group"] = {"backend": dist.get_backend(), "timeout_s": PG_TIMEOUT_S}
         elif world > 1:
             line["process_group"] = {"backend": dist.get_backend(), "timeout_s": PG_TIMEOUT_S}
             line["client_shard"] = cs

@@ -10,5 +10,5 @@ run() { local name=$1 t=$2; shift 2; echo "=== $name ($(date +%T))"; timeout -k 
         echo "=== $name rc=$rc"; tail -n 8 "$OUT/$name.log"; [ $rc -eq 0 ] || exit $rc; }
 run pytest_gpu 900 python -u -m pytest ${FILES:-tests} -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread
 [ "${SMOKE:-1}" = "1" ] && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-[ "${TORCHRUN:-0}" = "1" ] && run bench_n2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 20 --warmup 5
+[ "${TORCHRUN:-0}" = "1" ] && run bench_n2 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 20 --warmup 5
 echo "=== done"

@@ -40,7 +40,10 @@ def main():
     from substrafl.dependency import Dependency
 
     out = {}
-    dep = Dependency(local_installable_dependencies=[ROOT], excluded_paths=[ROOT / p for p in EXCLUDED])
+    # only what is there: the reference refuses an excluded path that does not exist (a checkout
+    # without history or build products has no .git, build/ or tuning library)
+    excluded = [ROOT / p for p in EXCLUDED if (ROOT / p).exists()]
+    dep = Dependency(local_installable_dependencies=[ROOT], excluded_paths=excluded)
     wheels = [Path(w) for w in dep._wheels]
     out["wheels"] = [w.name for w in wheels]
     whl = dep.cache_directory / wheels[0]

@@ -27,7 +27,7 @@ def _bench(*args, timeout=240):
 
 
 def test_default_line_fields():
-    line = _bench("--workload", "c2", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1")
+    line = _bench("--full", "--workload", "c2", "--steps", "5", "--warmup", "2", "--cpu-seconds", "1")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                 "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line
@@ -43,8 +43,64 @@ def test_default_line_fields():
     assert line["parity"]["mismatches"] == 0
 
 
+MOVED_BEHIND_FULL = (("cpu_baseline",), ("parity",), ("roofline", "read_stream_ceiling_GBps"),
+                     ("roofline", "frac_of_read_ceiling"), ("roofline", "kernel_ms_median"),
+                     ("roofline", "kernel_ms_min"), ("roofline", "traffic"))
+
+
+def _dumped(line, d, names):
+    import numpy as np
+
+    arrays = {n: np.load(d / f"{n}.npy") for n in names}
+    assert sorted(p.name for p in d.iterdir()) == sorted(f"{n}.npy" for n in names)
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    for n, a in arrays.items():
+        rec = line["dumped_outputs"][f"{n}.npy"]
+        assert a.ndim == 1 and a.size == rec["elements"] > 0 and str(a.dtype) == rec["dtype"]
+        assert np.isfinite(a).all() and np.abs(a).max() > 0
+    return arrays
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """No --full: the line keeps the headline fields (value, ms_per_step over exactly --steps timed
+    steps) and every figure that takes a run of its own is null; --dump-outputs writes the last
+    step's result (25M fp32 > the size limit: the fixed sample).  The same arguments with --full
+    dump the very same bits, and there the spot check ties them to the reference's order."""
+    import numpy as np
+
+    args = ("--gpus", "1", "--workload", "c2", "--steps", "4", "--warmup", "1")
+    plain = _bench(*args, "--dump-outputs", str(tmp_path / "plain"))
+    assert plain["full"] is False and plain["steps"] == 4 and plain["warmup"] == 1
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["unit"] == "GB/s" and plain["dtype"] == "f32"
+    assert plain["higher_is_better"] is True and plain["metric"].startswith("aggregated-param GB/s")
+    from_ms = plain["config"]["bytes_alg_per_step_job"] / plain["ms_per_step"] / 1e6  # GB/s of one timed step
+    assert abs(plain["value"] - from_ms) < 1e-3 * plain["value"]
+    for path in MOVED_BEHIND_FULL:
+        v = plain
+        for k in path:
+            v = v[k]
+        assert v is None, path
+    a = _dumped(plain, tmp_path / "plain", ["out"])["out"]
+    assert a.dtype == np.float32 and plain["dumped_outputs"]["out.npy"]["sampled"] is True
+    full = _bench(*args, "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full"))
+    assert full["full"] is True and full["parity"]["mismatches"] == 0
+    b = _dumped(full, tmp_path / "full", ["out"])["out"]
+    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def test_plain_scaffold_run_dumps_both_outputs(tmp_path):
+    """Scaffold (c4): the two fp64 results of the last step, sampled at the same elements."""
+    import numpy as np
+
+    line = _bench("--gpus", "1", "--workload", "c4", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert line["full"] is False and line["parity"] is None and line["dtype"] == "f32-in/f64-acc"
+    got = _dumped(line, tmp_path, ["dout", "cout"])
+    assert got["dout"].dtype == np.float64 and got["dout"].shape == got["cout"].shape
+    assert not np.array_equal(got["dout"], got["cout"])
+
+
 def test_scaffold_line():
-    line = _bench("--workload", "c4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--full", "--workload", "c4", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     assert line["dtype"] == "f32-in/f64-acc" and line["parity"]["mismatches"] == 0
     assert line["roofline"]["kernel"].startswith("scaffold_bucket_kernel<float> x2")  # 16 clients: one bucket per launch
 
@@ -64,7 +120,7 @@ def test_client_shard_single_rank(combine):
 def test_shared_gpu_ranks_skip_the_client_shard_leg():
     """Two ranks sharing the one GPU of a test box: the parameter-range line is measured, the
     client-shard leg (RCCL needs a GPU per rank) is reported as skipped."""
-    line = _bench("--workload", "c2", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--full", "--workload", "c2", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     assert line["n_gpus"] == 2 and "skipped" in line["client_shard"]
     assert line["process_group"]["timeout_s"] > 0
 
@@ -111,7 +167,8 @@ def test_multi_device_engine_line():
 def test_tiled_layout_line():
     """--layout tiles (c2: the few-client tile) and the default auto (c2: rows, below the
     recommended shape): both parity-clean, the layout named in the config."""
-    tiles = _bench("--workload", "c2", "--layout", "tiles", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    tiles = _bench("--full", "--workload", "c2", "--layout", "tiles", "--steps", "3", "--warmup", "1",
+                   "--no-cpu-baseline")
     assert tiles["parity"]["mismatches"] == 0
     assert tiles["config"]["layout"].startswith("tile-interleaved (2048")
     auto = _bench("--workload", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
@@ -120,7 +177,7 @@ def test_tiled_layout_line():
 
 def test_default_workload_line():
     """The driver's own command shape on the default workload (C3, tile-interleaved buckets)."""
-    line = _bench("--steps", "3", "--warmup", "1", "--no-cpu-baseline")
+    line = _bench("--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline")
     assert line["config"]["workload"] == "fedavg_fp32_64x125M"
     assert line["config"]["layout"].startswith("tile-interleaved (8192")
     assert line["parity"]["mismatches"] == 0 and 0.5 < line["roofline"]["frac"] < 1

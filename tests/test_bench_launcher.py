@@ -31,11 +31,21 @@ CLIENT_SHARD_FIELDS = ("combine", "scaling", "clients", "clients_per_gpu", "para
                        "weak_efficiency", "bit_exact_by_construction", "schedule", "parity")
 
 
+def test_gpus_2_without_full_runs_no_leg():
+    """Without --full the N > 1 command is the parameter-range line alone: two ranks, no leg."""
+    r = _run(["--gpus", "2", "--rehearse-cpu", "--steps", "3", "--warmup", "1"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _line(r.stdout)
+    assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["steps"] == 3 and line["ms_per_step"] > 0
+    assert 0 < line["process_group"]["timeout_s"] <= 600
+    assert not {"client_shard", "legs_order", "param_range_strong_gather"} & set(line)
+
+
 def test_plain_gpus_2_launches_two_ranks():
-    """The plain N > 1 command: one line with the parameter-range fields AND the client-shard leg
+    """The N > 1 command with --full: one line with the parameter-range fields AND the client-shard leg
     (the north-star mode: lockstep schedule over one communicator, here gloo on a tiny problem),
     and a process group with a finite timeout."""
-    r = _run(["--gpus", "2", "--rehearse-cpu", "--steps", "3", "--warmup", "1"])
+    r = _run(["--full", "--gpus", "2", "--rehearse-cpu", "--steps", "3", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r.stdout)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["rehearsal"] is True
@@ -124,7 +134,7 @@ def test_default_rounds_follow_the_executor():
 
 
 def test_plain_gpus_3_launches_three_ranks():
-    r = _run(["--gpus", "3", "--rehearse-cpu", "--steps", "2", "--warmup", "0", "--combine", "relay"])
+    r = _run(["--full", "--gpus", "3", "--rehearse-cpu", "--steps", "2", "--warmup", "0", "--combine", "relay"])
     assert r.returncode == 0, r.stderr[-3000:]
     line = _line(r.stdout)
     assert line["n_gpus"] == 3 and line["client_shard"]["combine"] == "relay"

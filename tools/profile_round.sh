@@ -36,12 +36,12 @@ print(_native.load().fedagg_scaffold_launches(16, 4, 25000000, 1))") ;;
     --out "$OUT/${TAG}_traffic_${WL}.json" > /dev/null
   # the bench line of this session carries the traffic just measured on this very build
   echo "[$TAG] $WL: bench" >&2
-  timeout -k 10 400 python3 "$ROOT/bench.py" --workload "$WL" --steps $STEPS --warmup 10 \
+  timeout -k 10 400 python3 "$ROOT/bench.py" --full --workload "$WL" --steps $STEPS --warmup 10 \
     --traffic "$OUT/${TAG}_traffic_${WL}.json" > "$OUT/${TAG}_bench_${WL}.json"
   echo "[$TAG] $WL: kernel trace" >&2
   rm -rf "$OUT/${TAG}_prof_${WL}"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof_${WL}" -o run -- \
-    python3 "$ROOT/bench.py" --workload "$WL" --steps $STEPS --warmup 10 --no-cpu-baseline \
+    python3 "$ROOT/bench.py" --full --workload "$WL" --steps $STEPS --warmup 10 --no-cpu-baseline \
     --traffic "$OUT/${TAG}_traffic_${WL}.json" > "$OUT/${TAG}_profiled_bench_${WL}.json"
   STATS=$(find "$OUT/${TAG}_prof_${WL}" -name '*kernel_stats.csv' | head -1)
   cp "$STATS" "$OUT/${TAG}_${WL}_kernel_stats.csv"

@@ -20,7 +20,7 @@ for WL in "$@"; do
     echo "[$TAG] $WL: pass $P" >&2
     rm -rf "$OUT/${TAG}_pmc${P}_${WL}"
     timeout -s KILL 240 rocprofv3 --pmc $CTRS --output-format csv -d "$OUT/${TAG}_pmc${P}_${WL}" -o run -- \
-      python3 "$ROOT/bench.py" --workload "$WL" --steps 10 --warmup 2 --no-cpu-baseline > /dev/null
+      python3 "$ROOT/bench.py" --full --workload "$WL" --steps 10 --warmup 2 --no-cpu-baseline > /dev/null
     cp "$(find "$OUT/${TAG}_pmc${P}_${WL}" -name '*counter_collection.csv' | head -1)" "$OUT/${TAG}_${WL}_pmc${P}.csv"
   done
 done
