@@ -439,7 +439,11 @@ enum {
   FEDAGG_U8 = 7, FEDAGG_U16 = 8, FEDAGG_U32 = 9, FEDAGG_U64 = 10, FEDAGG_BOOL = 11,
 };
 /* out[i] = (out_kind) in[i]: integer/bool -> float as NumPy's astype (round to nearest),
- * float widening exact.  Used for integer layers (x_int * python_float is a float64 loop). */
+ * float widening exact.  Float narrowing (f64 -> f32, f64 -> f16, f32 -> f16) is one
+ * round-to-nearest-even step from the source value: overflow goes to +-inf, subnormal results
+ * are kept (never flushed), NaN stays NaN.  Every in_kind pairs with every float out_kind;
+ * 64-bit integers -> f16 go through float like NumPy (|v| < 2^24 is exact there, and everything
+ * from 65520 up is +-inf).  Used for integer layers (x_int * python_float is a float64 loop). */
 int fedagg_cast(const void* d_in, int in_kind, void* d_out, int out_kind, uint64_t n, void* stream);
 /* out[i] = (out_kind) fl_in(in[i] * fl_in(w)): one client's product in its own float type,
  * then widened -- a layer whose clients carry different dtypes (fed_avg.py:221-222 stacks the

@@ -1425,7 +1425,8 @@ __global__ void __launch_bounds__(FA_BLOCK)
 // ------------------------------------------------------------------------------------
 // dtype plumbing on the device (exact widening casts; per-client pre-scaling for layers whose
 // clients do not share one dtype) -- NumPy semantics: int/bool -> float64 is the C cast
-// (round to nearest), float widening is exact, x * w is computed in x's own float type.
+// (round to nearest), float widening is exact, float narrowing is one round-to-nearest-even
+// step from the source value, x * w is computed in x's own float type.
 // ------------------------------------------------------------------------------------
 template <typename TI>
 __device__ __forceinline__ double ld_as_double(const void* p, uint64_t i) {
@@ -1459,9 +1460,14 @@ __global__ void __launch_bounds__(FA_BLOCK)
       if (out_kind == FEDAGG_F64)
         static_cast<double*>(out)[i] = in_kind == FEDAGG_I64 ? (double)static_cast<const int64_t*>(in)[i]
                                                             : (double)static_cast<const uint64_t*>(in)[i];
-      else
-        static_cast<float*>(out)[i] = in_kind == FEDAGG_I64 ? (float)static_cast<const int64_t*>(in)[i]
-                                                           : (float)static_cast<const uint64_t*>(in)[i];
+      else {
+        const float f = in_kind == FEDAGG_I64 ? (float)static_cast<const int64_t*>(in)[i]
+                                              : (float)static_cast<const uint64_t*>(in)[i];
+        if (out_kind == FEDAGG_F32)
+          static_cast<float*>(out)[i] = f;
+        else  // fp16 goes through float, as NumPy's does: exact below 2^24, +-inf from 65520 up
+          static_cast<_Float16*>(out)[i] = (_Float16)f;
+      }
       continue;
     }
     const double v = load_kind(in, in_kind, i);  // exact for every other supported input

@@ -187,6 +187,123 @@ def _same64(a, b):
                                                                       b.contiguous().view(torch.int64))
 
 
+# ----------------------------------------------------------------------------------------
+# flat client ops on layer lists a model does not give: empty layers first, in the middle and
+# last, flat offsets that are no multiple of 4, a chunk boundary +-1, a first launch group that is
+# all empty -- with non-finite values, against the reference's torch expressions on CPU tensors
+# ----------------------------------------------------------------------------------------
+GEOMETRIES = {
+    "edges": [0, 1, 3, 4, 5, 8191, 8192, 8193, 0, 16385, 2, 0],
+    # the first launch group is all empty: it launches nothing and the flat offset carries across it
+    "empty-first-group": [0] * 32 + [5, 0, 8193, 1, 3, 7, 2, 4],
+}
+COEFFS = [0.1, -1.0 / (0.05 * 7), 1.0 / 3.0, -1.0]  # none but the last representable in fp32
+
+
+def _operand(numel, dtype, seed):
+    """CPU layers of ``numel`` elements: normal values with +-0, denormals, +-inf, NaN and +-(fp32
+    max) spread over a fifth of them (each special present in every operand)."""
+    g = torch.Generator().manual_seed(seed)
+    n = sum(numel)
+    flat = torch.randn(n, generator=g, dtype=dtype) * 3
+    f32max = torch.finfo(torch.float32).max
+    specials = torch.tensor([0.0, -0.0, 1e-40, -1e-42, float("inf"), -float("inf"), float("nan"), f32max, -f32max,
+                             1e-310 if dtype == torch.float64 else 1e-45], dtype=dtype)
+    assert specials[2] != 0 and specials[-1] != 0  # denormals survived the conversion
+    pick = torch.rand(n, generator=g) < 0.2
+    flat[pick] = specials[torch.randint(0, len(specials), (int(pick.sum()),), generator=g)]
+    bits = flat.view(torch.int32 if dtype == torch.float32 else torch.int64)
+    for v in specials:  # every special is there, by bit pattern (NaN by NaN-ness)
+        assert torch.isnan(flat).any() if torch.isnan(v) else (bits == v.view(bits.dtype)).any()
+    return [t.clone() for t in torch.split(flat, numel)]
+
+
+def _cuda(layers):
+    return [t.cuda() for t in layers]
+
+
+def _same_nan_aware(got, ref):
+    """Bit for bit where the reference is a number, NaN where it is NaN."""
+    got, ref = got.detach().cpu().contiguous(), ref.detach().contiguous()
+    if got.shape != ref.shape or got.dtype != ref.dtype:
+        return False
+    nan = torch.isnan(ref)
+    ib = torch.int32 if ref.dtype == torch.float32 else torch.int64
+    return torch.equal(torch.isnan(got), nan) and torch.equal(got.view(ib)[~nan], ref.view(ib)[~nan])
+
+
+def _raw_equal(got, ref):
+    got, ref = got.detach().cpu().contiguous(), ref.detach().cpu().contiguous()
+    return got.shape == ref.shape and got.dtype == ref.dtype and torch.equal(got.view(torch.int32), ref.view(torch.int32))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geometry", list(GEOMETRIES))
+def test_flat_gather_then_scatter_round_trips(flat_path, geometry):
+    """``fedagg_flat_scatter_f32`` (flat bucket -> layers): gather, then scatter into fresh layers;
+    copies keep every bit, NaN payloads included."""
+    from substrafl_amd import _native
+
+    numel = GEOMETRIES[geometry]
+    src = _operand(numel, torch.float32, 1)
+    dev = _cuda(src)
+    flat = wm._gather_flat(dev)
+    assert _raw_equal(flat, torch.cat(src))
+    flat2 = torch.full((sum(numel) + 64,), 7.0, device="cuda")  # the f32 entry point, with room behind the bucket
+    lib = _native.load()
+    ptrs = lambda ts: _native.ptr_array([t.data_ptr() for t in ts])  # noqa: E731
+    stream = wm._stream(flat2.device)
+    _native.check(lib.fedagg_flat_gather_f32(ptrs(dev), wm._numel_array(dev), len(dev), flat2.data_ptr(), stream),
+                  "flat_gather_f32")
+    assert _raw_equal(flat2[:sum(numel)], torch.cat(src)) and bool((flat2[sum(numel):] == 7.0).all())
+    fresh = [torch.full((n + 8,), 7.0, device="cuda") for n in numel]  # 8 guard elements behind every layer
+    dst = [t[:n] for t, n in zip(fresh, numel)]
+    _native.check(lib.fedagg_flat_scatter_f32(ptrs(dst), wm._numel_array(dst), len(dst), flat.data_ptr(), stream),
+                  "flat_scatter_f32")
+    for d, s, f, n in zip(dst, src, fresh, numel):
+        assert _raw_equal(d, s) and bool((f[n:] == 7.0).all())
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geometry", list(GEOMETRIES))
+@pytest.mark.parametrize("kinds", [("f32", "f32", "f64", "f32"), ("f64", "f32", "f32"), ("f32", "f32", "f32"),
+                                   ("f32", "f32", "f32", "f32")], ids="-".join)
+def test_flat_wsum_three_and_four_lists_vs_torch_on_cpu(flat_path, kinds, geometry):
+    numel = GEOMETRIES[geometry]
+    dts = [torch.float64 if k == "f64" else torch.float32 for k in kinds]
+    lists = [_operand(numel, dt, 10 + j) for j, dt in enumerate(dts)]
+    coeffs = COEFFS[:len(kinds)]
+    ref = ref_wsum(lists, coeffs)  # weight_manager.py:205-210 on the CPU
+    got = wm.weighted_sum_parameters([_cuda(lst) for lst in lists], coeffs)
+    want = torch.float64 if "f64" in kinds else torch.float32
+    assert len(got) == len(ref) and all(g.dtype == want and g.is_cuda for g in got)
+    # views of ONE bucket: the fused launch made them, not the torch loop
+    assert len({g.untyped_storage().data_ptr() for g in got if g.numel()}) == 1
+    assert all(_same_nan_aware(g, r) for g, r in zip(got, ref))
+
+
+class _Layers(torch.nn.Module):
+    def __init__(self, layers):
+        super().__init__()
+        self.ps = torch.nn.ParameterList([torch.nn.Parameter(t.clone()) for t in layers])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("geometry", list(GEOMETRIES))
+@pytest.mark.parametrize("flat_dtype", [torch.float32, torch.float64], ids=["f32", "f64"])
+def test_flat_increment_vs_torch_on_cpu(flat_path, flat_dtype, geometry):
+    numel = GEOMETRIES[geometry]
+    w0 = _operand(numel, torch.float32, 20)
+    u = _operand(numel, flat_dtype, 21)
+    m_ref, m = _Layers(w0), _Layers(w0).cuda()
+    with torch.no_grad():
+        for w, x in zip(m_ref.ps, u):
+            w.data += 0.1 * x.data  # weight_manager.py:137
+    wm.increment_parameters(m, _cuda(u), with_batch_norm_parameters=True, updates_multiplier=0.1)
+    assert all(p.dtype == torch.float32 for p in m.ps)
+    assert all(_same_nan_aware(a.data, b.data) for a, b in zip(m.ps, m_ref.ps))
+
+
 def test_host_result_buffer_reused_only_when_released():
     """D2H result buffers (export_numpy, the engine's outputs) are recycled across calls (no 100 MB
     of fresh page faults per call) only when no array handed out from them is alive."""
