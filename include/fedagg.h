@@ -430,6 +430,31 @@ int fedagg_flat_wsum(const void* const* d_layers, const int* kinds, int nlists, 
                      const uint64_t* numel, int L, void* d_flat, int flat_kind, void* stream);
 int fedagg_flat_increment(float* const* d_layers, const uint64_t* numel, int L, const void* d_flat, int flat_kind,
                           double multiplier, void* stream);
+/* 16-bit models (kinds FEDAGG_F16 / FEDAGG_BF16; weight_manager.py:103-212 on a model.half() or
+ * model.to(torch.bfloat16)).  torch computes each op on these dtypes in fp32 and rounds its
+ * result once to the tensor's type (fl_T below), a Python scalar is rounded to fp32; fp32 -> bf16
+ * rounds to nearest even, overflow goes to +-inf, NaN stays NaN (payloads unspecified).
+ *   gather:    fedagg_flat_gather with kind F16 / BF16: 2-byte copies into a flat bucket of that kind.
+ *   wsum:      fedagg_flat_wsum with EVERY list and d_flat of one 16-bit kind T:
+ *              p_j = fl_T(fl32(x_j) * fl32(c_j)); acc = fl_T(0.0f + fl32(p_0)) (-0 becomes +0);
+ *              acc = fl_T(fl32(acc) + fl32(p_j)).  A 16-bit list next to an F32 / F64 list, or F16
+ *              next to BF16, is FEDAGG_EINVAL (torch's promotion is left to torch).
+ *   increment: fedagg_flat_increment_kind, (layer_kind, flat_kind) one of
+ *              (F16, F16), (BF16, BF16):  w = fl_T(fl32(w) + fl32(fl_T(fl32(m) * fl32(u))))
+ *              (BF16, F32):               w = bf16(fl32(w) + t), t = fl32(fl32(m) * u)  -- the engine's
+ *                                         fp32 average applied to a bf16 model (promoted in-place add).
+ *                                         In a layer's leading floor(numel / 16384) * 16384 elements t
+ *                                         is rounded to bf16 first: torch on ROCm (2.10) adds an aligned
+ *                                         contiguous bf16 tensor and an fp32 tensor that way in every full
+ *                                         block of 16384 elements (its type-specialised vectorised kernel
+ *                                         converts both inputs to the output type) and rounds once in the
+ *                                         remainder; the reference's per-layer tensors are such tensors.
+ *              every other pair is FEDAGG_EINVAL (fedagg_flat_increment keeps fp32 parameters).
+ * With "flat_vec" a layer whose pointers are 16-B aligned moves 8 elements per lane; its slice
+ * of a 16-bit flat bucket is accessed 16 B at a time only where it starts at an even element
+ * (4-B aligned), else 2 bytes at a time. */
+int fedagg_flat_increment_kind(void* const* d_layers, int layer_kind, const uint64_t* numel, int L,
+                               const void* d_flat, int flat_kind, double multiplier, void* stream);
 
 /* ---------------------------------------------------------------------------
  * dtype plumbing (device side, NumPy semantics).  Kinds: */

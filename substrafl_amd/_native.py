@@ -62,6 +62,7 @@ SIGNATURES = {
     "fedagg_flat_gather": (c_int, [P(c_void), c_int, P(c_u64), c_int, c_void, c_void]),
     "fedagg_flat_wsum": (c_int, [P(c_void), P(c_int), c_int, P(c_dbl), P(c_u64), c_int, c_void, c_int, c_void]),
     "fedagg_flat_increment": (c_int, [P(c_void), P(c_u64), c_int, c_void, c_int, c_dbl, c_void]),
+    "fedagg_flat_increment_kind": (c_int, [P(c_void), c_int, P(c_u64), c_int, c_void, c_int, c_dbl, c_void]),
     "fedagg_scale_cast": (c_int, [c_void, c_int, c_dbl, c_void, c_int, c_u64, c_void]),
     # client-sharded building blocks (chain / split pairwise trees)
     "fedagg_fedavg_chain_f32": (c_int, [P(c_void), P(ctypes.c_float), c_int, c_u64, c_int, c_void, c_void]),

@@ -5,15 +5,19 @@ Same functions, signatures and results as the reference's
 :79-100, ``increment_parameters`` :103-137, ``subtract_parameters`` :140-158, ``add_parameters``
 :161-179, ``weighted_sum_parameters`` :182-212, ``set_parameters`` :215-238,
 ``zeros_like_parameters`` :241-265), so an algorithm can switch its import.  When every tensor is
-fp32 on a ROCm device the per-layer torch loops become single launches of libfedagg's flat-bucket
-kernels, and the tensors they return are views of ONE flat device bucket -- which
+fp32 (or every tensor fp16, or bf16) on a ROCm device the per-layer torch loops become single
+launches of libfedagg's flat-bucket kernels, and the tensors they return are views of ONE flat device bucket -- which
 :func:`export_numpy` brings home with a single D2H copy (the wire format the aggregator stages
 with one contiguous segment per client).  Other dtypes and CPU tensors keep the reference's torch
 semantics (they are the client's own device choice, not the aggregation hot path).
 
 Bit-exact with the reference's torch ops: ``weighted_sum_parameters`` is Python ``sum()`` from int 0
 over ``param * coeff`` (so ``-0.0`` becomes ``+0.0``, and ``coeff`` is rounded to fp32 as torch does
-for a Python scalar); ``increment_parameters`` is ``w += fl32(multiplier) * u``.
+for a Python scalar); ``increment_parameters`` is ``w += fl32(multiplier) * u``.  On fp16 / bf16
+tensors torch computes each op in fp32 and rounds its result once to the tensor's type; a bf16
+model takes an fp32 update (the aggregator's average of ``wire.BF16`` buckets) with the add in the
+promoted fp32, as torch on ROCm performs it on the reference's per-layer tensors (the update
+rounded to bf16 first in each full 16384-element block of a layer; include/fedagg.h states the rules).
 """
 
 from __future__ import annotations
@@ -26,7 +30,7 @@ import torch
 from torch._utils import _unflatten_dense_tensors
 
 from .. import _native
-from ..wire import bucket_views, flat_of
+from ..wire import BF16, bucket_views, flat_of
 
 _BN = (
     torch.nn.BatchNorm1d,
@@ -66,12 +70,21 @@ def model_parameters(model: torch.nn.Module, with_batch_norm_parameters: bool):
 # ----------------------------------------------------------------------------------------
 # flat-bucket helpers
 # ----------------------------------------------------------------------------------------
-_KIND = {torch.float32: _native.FEDAGG_F32, torch.float64: _native.FEDAGG_F64}
+_KIND = {torch.float32: _native.FEDAGG_F32, torch.float64: _native.FEDAGG_F64,
+         torch.float16: _native.FEDAGG_F16, torch.bfloat16: _native.FEDAGG_BF16}
+_KIND16 = (_native.FEDAGG_F16, _native.FEDAGG_BF16)
+# (parameter kind, update kind) pairs of the 16-bit increment (fedagg_flat_increment_kind): a
+# 16-bit model takes an update of its own kind, a bf16 model also the engine's fp32 average
+_INC16 = {(_native.FEDAGG_F16, _native.FEDAGG_F16), (_native.FEDAGG_BF16, _native.FEDAGG_BF16),
+          (_native.FEDAGG_BF16, _native.FEDAGG_F32)}
+# host dtypes staged as raw bytes into a device bucket of the torch dtype
+_HOST_DTYPE = {np.dtype(np.float32): torch.float32, np.dtype(np.float64): torch.float64,
+               np.dtype(np.float16): torch.float16, BF16: torch.bfloat16}
 
 
 def _kind(tensors: Sequence[torch.Tensor], device=None) -> Optional[int]:
-    """The libfedagg kind when ``tensors`` are contiguous ROCm tensors of ONE dtype (fp32 or fp64)
-    on one device (``device`` if given); else None (the op keeps the reference's torch loop)."""
+    """The libfedagg kind when ``tensors`` are contiguous ROCm tensors of ONE dtype (fp32, fp64,
+    fp16 or bf16) on one device (``device`` if given); else None (the op keeps the reference's torch loop)."""
     if not tensors:
         return None
     t0 = tensors[0]
@@ -89,10 +102,6 @@ def _kind(tensors: Sequence[torch.Tensor], device=None) -> Optional[int]:
         if t.dtype != dt or t.get_device() != idx or not t.is_contiguous():
             return None
     return _KIND[dt]
-
-
-def _fast(tensors: Sequence[torch.Tensor]) -> bool:
-    return _kind(tensors) == _native.FEDAGG_F32
 
 
 def _numel_array(tensors):
@@ -167,9 +176,20 @@ def increment_parameters(
                 f"The shape of the model weights ({w.data.shape}) and of the update ({u.shape}) "
                 "passed in the updates argument are unequal."
             )
-        if _fast([p.data for p in params]):
+        pkind = _kind([p.data for p in params])
+        if pkind in _KIND16:
             flat = _device_flat(updates, params[0].device)
-            if flat is not None:
+            if flat is not None and (pkind, _KIND[flat.dtype]) in _INC16:
+                lib = _native.load()
+                _native.check(lib.fedagg_flat_increment_kind(_native.ptr_array([p.data.data_ptr() for p in params]),
+                                                             pkind, _numel_array(params), len(params),
+                                                             flat.data_ptr(), _KIND[flat.dtype],
+                                                             float(updates_multiplier), _stream(flat.device)),
+                              "flat_increment_kind")
+                return
+        elif pkind == _native.FEDAGG_F32:
+            flat = _device_flat(updates, params[0].device)
+            if flat is not None and flat.dtype in (torch.float32, torch.float64):
                 lib = _native.load()
                 _native.check(lib.fedagg_flat_increment(_native.ptr_array([p.data.data_ptr() for p in params]),
                                                         _numel_array(params), len(params), flat.data_ptr(),
@@ -177,19 +197,21 @@ def increment_parameters(
                                                         _stream(flat.device)), "flat_increment")
                 return
         for w, u in zip(params, updates):
-            u = torch.from_numpy(u).to(w.device) if isinstance(u, np.ndarray) else u
+            if isinstance(u, np.ndarray):
+                u = (torch.from_numpy(u.view(np.int16)).view(torch.bfloat16) if u.dtype == BF16
+                     else torch.from_numpy(u)).to(w.device)
             w.data += updates_multiplier * u.data
 
 
 def _device_flat(updates, device) -> Optional[torch.Tensor]:
-    """One device bucket (fp32 or fp64) holding ``updates`` back to back, None if they are not all
-    of one of those dtypes."""
+    """One device bucket (fp32, fp64, fp16 or bf16) holding ``updates`` back to back, None if they
+    are not all of one of those dtypes (host layers: float32 / float64 / float16 / ``wire.BF16``)."""
     if all(isinstance(u, torch.Tensor) for u in updates):
         if _kind(updates, device) is None:
             return None
         flat = flat_bucket(updates)
         return flat if flat is not None else _gather_flat(updates)
-    if all(isinstance(u, np.ndarray) for u in updates) and updates[0].dtype in (np.float32, np.float64) and all(
+    if all(isinstance(u, np.ndarray) for u in updates) and updates[0].dtype in _HOST_DTYPE and all(
             u.dtype == updates[0].dtype for u in updates):
         return _stage_host_layers(updates, torch.device(device))
     return None
@@ -208,7 +230,7 @@ def _stage_host_layers(arrays: Sequence[np.ndarray], device) -> torch.Tensor:
     idx = device.index if device.index is not None else torch.cuda.current_device()
     layers = [np.ascontiguousarray(a) for a in arrays]
     n = sum(int(a.size) for a in layers)
-    dt = torch.float64 if layers[0].dtype == np.float64 else torch.float32  # the caller checked: one of the two
+    dt = _HOST_DTYPE[layers[0].dtype]  # the caller checked; 16-bit layers travel as their raw bytes
     flat = torch.empty(n, dtype=dt, device=torch.device("cuda", idx))
     if n:
         # the bucket may reuse memory torch's stream still reads: the copy starts after that stream
@@ -254,9 +276,14 @@ def weighted_sum_parameters(parameters_list: List[List[torch.Tensor]], coefficie
             parameters_to_sum[0].data.shape == parameter.data.shape for parameter in parameters_to_sum
         ), "The shape of the parameters are unequal."
     kinds = [_kind(lst, parameters_list[0][0].device if parameters_list[0] else None) for lst in parameters_list]
-    if 1 <= len(parameters_list) <= _native.FEDAGG_FLAT_MAX_LISTS and all(k is not None for k in kinds):
+    # a 16-bit list next to a list of another kind follows torch's promotion: left to torch
+    if 1 <= len(parameters_list) <= _native.FEDAGG_FLAT_MAX_LISTS and all(k is not None for k in kinds) and (
+            not any(k in _KIND16 for k in kinds) or len(set(kinds)) == 1):
         like = parameters_list[0]
-        out_dtype = torch.float64 if _native.FEDAGG_F64 in kinds else torch.float32
+        if kinds[0] in _KIND16:
+            out_dtype = like[0].dtype
+        else:
+            out_dtype = torch.float64 if _native.FEDAGG_F64 in kinds else torch.float32
         with torch.no_grad():
             out = torch.empty(sum(t.numel() for t in like), dtype=out_dtype, device=like[0].device)
             lib = _native.load()
@@ -315,12 +342,14 @@ def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = 
     from .. import handoff, runtime
 
     # one D2H through the native session's pinned ring (chunked, copied out by its worker pool)
-    host = runtime.reusable_host_array(flat.numel(), torch.empty(0, dtype=flat.dtype).numpy().dtype,
-                                       tag)  # bf16 raises, as .numpy()
+    # a bf16 bucket comes home as wire.BF16 (its bit patterns); any other dtype NumPy lacks raises, as .numpy()
+    host_dt = BF16 if flat.dtype == torch.bfloat16 else torch.empty(0, dtype=flat.dtype).numpy().dtype
+    host = runtime.reusable_host_array(flat.numel(), host_dt, tag)
     torch.cuda.current_stream(flat.device).synchronize()  # the bucket was written on torch's stream
     with runtime.device_lock(flat.device.index):  # the session's ring is shared with the engine
         runtime.session(flat.device.index).fetch(flat.data_ptr(), host)
-    handoff.record_tensor(host, flat)  # simulation mode (opt-in): freezes host, keeps flat for the aggregator
+    if flat.element_size() != 2:  # 16-bit exports are not handed off: the aggregator stages them from the host
+        handoff.record_tensor(host, flat)  # simulation mode (opt-in): freezes host, keeps flat for the aggregator
     shapes = [tuple(t.shape) for t in tensors]
     if wire:
         return bucket_views(host, shapes)
@@ -338,7 +367,8 @@ def to_device(arrays: Sequence[np.ndarray], device) -> List[torch.Tensor]:
     flat bucket, returned as per-layer views (so the flat kernels take the bucket as is)."""
     arrays = list(arrays)
     d = torch.device(device)
-    if d.type == "cuda" and arrays and all(isinstance(a, np.ndarray) for a in arrays):
+    if d.type == "cuda" and arrays and all(isinstance(a, np.ndarray) and a.dtype in (np.float32, np.float64)
+                                           for a in arrays):
         flat = _device_flat(arrays, d)
         if flat is not None:
             shapes = [a.shape for a in arrays]

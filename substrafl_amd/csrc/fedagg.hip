@@ -1702,6 +1702,243 @@ int flat_seg_launch(const void* const* ptrs, const int* kinds, int nlists, const
 }
 
 // ------------------------------------------------------------------------------------
+// 16-bit kinds of the client flat ops (fp16 and bf16 models).  torch's arithmetic for these
+// dtypes: every op computes in fp32 (opmath) and rounds its result once to the tensor's type, a
+// Python scalar is rounded to fp32.  K is the 16-bit kind (elements handled as their bit
+// patterns), FLAT32 says the flat bucket is fp32 (increment of a bf16 model by the engine's fp32
+// average: the promoted in-place add, w = bf16(fl32(w) + fl32(fl32(m) * u)), with the update
+// rounded to bf16 first in a layer's leading full 16384-element blocks, see seg16_inc32).
+//   wsum:      p_j = fl_K(fl32(x_j) * fl32(c_j)); acc = fl_K(0.0f + p_0); acc = fl_K(acc + p_j)
+//   increment: w = fl_K(fl32(w) + fl32(fl_K(fl32(m) * fl32(u))))
+// ------------------------------------------------------------------------------------
+template <int K>
+__device__ __forceinline__ float h16_to_f32(uint16_t b) {
+  if constexpr (K == FEDAGG_F16) return (float)__builtin_bit_cast(_Float16, b);
+  else return __uint_as_float((uint32_t)b << 16);
+}
+
+// fp32 -> 16 bits, round to nearest even, overflow to +-inf, NaN stays NaN (quiet bit set)
+template <int K>
+__device__ __forceinline__ uint16_t f32_to_h16(float f) {
+  if constexpr (K == FEDAGG_F16) {
+    // The fp32 value and the converted bits each pass through a register of their own, so the
+    // rounding is one plain v_cvt_f16_f32 of the fp32 result: the compiler neither folds the
+    // multiply before it into a mixed-precision fma nor pairs two conversions into a packed one.
+    asm("" : "+v"(f));
+    uint32_t r = __builtin_bit_cast(uint16_t, (_Float16)f);
+    asm("" : "+v"(r));
+    return (uint16_t)r;
+  } else {
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
+    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+  }
+}
+
+struct H8 {
+  uint16_t v[8];
+};
+struct F8 {
+  float v[8];
+};
+typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+__device__ __forceinline__ H8 h8_unpack(const u32x4 r) {
+  H8 o;
+  o.v[0] = (uint16_t)r.x, o.v[1] = (uint16_t)(r.x >> 16), o.v[2] = (uint16_t)r.y, o.v[3] = (uint16_t)(r.y >> 16);
+  o.v[4] = (uint16_t)r.z, o.v[5] = (uint16_t)(r.z >> 16), o.v[6] = (uint16_t)r.w, o.v[7] = (uint16_t)(r.w >> 16);
+  return o;
+}
+__device__ __forceinline__ u32x4 h8_pack(const H8& h) {
+  u32x4 r;
+  r.x = h.v[0] | ((uint32_t)h.v[1] << 16), r.y = h.v[2] | ((uint32_t)h.v[3] << 16);
+  r.z = h.v[4] | ((uint32_t)h.v[5] << 16), r.w = h.v[6] | ((uint32_t)h.v[7] << 16);
+  return r;
+}
+// 8 elements at p: a 16-B aligned layer, or (h8_*_a4) a 4-B aligned slice of the flat bucket --
+// the access the fp32 form uses for its slice.  There is no form for a 2-B aligned address:
+// eight 2-byte accesses of one lane would be merged into one wide access by the compiler.
+__device__ __forceinline__ H8 h8_load(const uint16_t* p) { return h8_unpack(*reinterpret_cast<const u32x4*>(p)); }
+__device__ __forceinline__ H8 h8_load_a4(const uint16_t* p) {
+  return h8_unpack(*reinterpret_cast<const u32x4a4*>(p));
+}
+__device__ __forceinline__ void h8_store(uint16_t* p, const H8& h) { *reinterpret_cast<u32x4*>(p) = h8_pack(h); }
+__device__ __forceinline__ void h8_store_a4(uint16_t* p, const H8& h) {
+  *reinterpret_cast<u32x4a4*>(p) = h8_pack(h);
+}
+
+template <int K>
+__device__ __forceinline__ uint16_t seg16_first(uint16_t x, float c) {
+#pragma clang fp contract(off)
+  const uint16_t p = f32_to_h16<K>(h16_to_f32<K>(x) * c);
+  return f32_to_h16<K>(0.0f + h16_to_f32<K>(p));  // Python sum() starts from int 0: -0 becomes +0
+}
+template <int K>
+__device__ __forceinline__ uint16_t seg16_next(uint16_t acc, uint16_t x, float c) {
+#pragma clang fp contract(off)
+  const uint16_t p = f32_to_h16<K>(h16_to_f32<K>(x) * c);
+  return f32_to_h16<K>(h16_to_f32<K>(acc) + h16_to_f32<K>(p));
+}
+template <int K>
+__device__ __forceinline__ uint16_t seg16_inc(uint16_t w, uint16_t u, float m) {
+#pragma clang fp contract(off)
+  const uint16_t t = f32_to_h16<K>(m * h16_to_f32<K>(u));
+  return f32_to_h16<K>(h16_to_f32<K>(w) + h16_to_f32<K>(t));
+}
+// A 16-bit parameter plus fl32(m * u) with u fp32.  torch's type promotion defines the in-place
+// add as the fp32 sum rounded once, and that is what its CPU kernels and its generic device
+// kernel give.  torch on ROCm (2.10) serves an aligned contiguous ``bf16 += fp32`` with a
+// type-specialised vectorised kernel (ATen/native/cuda/CUDALoops.cuh, rt_binary_specializations
+// {BFloat16, BFloat16, float}) whose loads convert both inputs to the OUTPUT type: in every full
+// block of FLAT_TORCH_MIXED_BLOCK elements of the tensor the fp32 operand is rounded to bf16
+// before the add; the remainder of the tensor goes through the generic kernel.  The reference's
+// tensors are whole aligned allocations (one ``.to(device)`` per layer), so a layer's leading
+// full blocks get two roundings there, and ``twice`` reproduces that here.
+#define FLAT_TORCH_MIXED_BLOCK 16384  // vectorized_templated_config: 512 threads x 32 elements
+static_assert(FLAT_TORCH_MIXED_BLOCK % SEG_CHUNK == 0, "a chunk lies inside one torch block or outside all of them");
+template <int K>
+__device__ __forceinline__ uint16_t seg16_inc32(uint16_t w, float u, float m, bool twice) {
+#pragma clang fp contract(off)
+  float t = m * u;
+  if (twice) t = h16_to_f32<K>(f32_to_h16<K>(t));
+  return f32_to_h16<K>(h16_to_f32<K>(w) + t);
+}
+
+// op 0: gather, 2: wsum, 3: increment, over 16-bit layers (the ops of flat_seg_kernel).  With
+// ``vec`` a layer moves 8 elements per lane when its pointers are all 16-B aligned AND its slice
+// of a 16-bit flat bucket starts at an even element (4-B aligned): 16-B accesses on the layers,
+// the 4-B aligned 16-B access on the slice.  An fp32 flat bucket (FLAT32) is always 4-B aligned
+// and read with two such loads.  Every other layer -- a slice at an odd element offset never sees
+// a multi-dword access -- and the last < 8 elements of a chunk go element by element, one
+// 2-byte access per lane, consecutive lanes on consecutive elements.
+template <int OP, int K, bool FLAT32>
+__global__ void __launch_bounds__(FA_BLOCK) flat_seg16_kernel(const SegArgs a, void* __restrict__ flat, int vec) {
+#pragma clang fp contract(off)
+  const int l = seg_of_block(a, blockIdx.x);
+  const uint64_t base = (uint64_t)(blockIdx.x - a.block_start[l]) * SEG_CHUNK;
+  const uint64_t n = a.n[l];
+  const uint64_t end = base + SEG_CHUNK < n ? base + SEG_CHUNK : n;
+  uint16_t* f16 = static_cast<uint16_t*>(flat) + a.flat_off[l];
+  const float* f32 = static_cast<const float*>(flat) + a.flat_off[l];
+  float cf[FEDAGG_FLAT_MAX_LISTS];
+#pragma unroll
+  for (int j = 0; j < FEDAGG_FLAT_MAX_LISTS; ++j) cf[j] = (float)a.coeff[j];  // torch rounds the scalar
+  uintptr_t bits = 0;
+  for (int j = 0; j < a.nlists; ++j) bits |= reinterpret_cast<uintptr_t>(a.p[j][l]);
+  const bool wide = vec && (bits & 15u) == 0 && (FLAT32 || (reinterpret_cast<uintptr_t>(f16) & 3u) == 0);
+  // (BF16, F32) only: chunks inside the layer's leading full torch blocks (a block is two chunks)
+  const bool twice = base < (n & ~(uint64_t)(FLAT_TORCH_MIXED_BLOCK - 1));
+  uint64_t tail = base + threadIdx.x;  // where the element-by-element loop starts
+  if (wide) {
+    const uint64_t vend = base + ((end - base) & ~(uint64_t)7);
+    for (uint64_t i = base + 8 * (uint64_t)threadIdx.x; i < vend; i += 8 * (uint64_t)FA_BLOCK) {
+      uint16_t* p0 = const_cast<uint16_t*>(static_cast<const uint16_t*>(a.p[0][l])) + i;
+      if constexpr (OP == 0) {
+        h8_store_a4(f16 + i, h8_load(p0));
+      } else if constexpr (OP == 2) {
+        H8 x = h8_load(p0), acc;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc.v[e] = seg16_first<K>(x.v[e], cf[0]);
+        for (int j = 1; j < a.nlists; ++j) {
+          x = h8_load(static_cast<const uint16_t*>(a.p[j][l]) + i);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) acc.v[e] = seg16_next<K>(acc.v[e], x.v[e], cf[j]);
+        }
+        h8_store_a4(f16 + i, acc);
+      } else {
+        H8 w = h8_load(p0);
+        if constexpr (FLAT32) {
+          const f32x4u u0 = *reinterpret_cast<const f32x4u*>(f32 + i);
+          const f32x4u u1 = *reinterpret_cast<const f32x4u*>(f32 + i + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            w.v[e] = seg16_inc32<K>(w.v[e], u0[e], cf[0], twice);
+            w.v[e + 4] = seg16_inc32<K>(w.v[e + 4], u1[e], cf[0], twice);
+          }
+        } else {
+          const H8 u = h8_load_a4(f16 + i);
+#pragma unroll
+          for (int e = 0; e < 8; ++e) w.v[e] = seg16_inc<K>(w.v[e], u.v[e], cf[0]);
+        }
+        h8_store(p0, w);
+      }
+    }
+    tail = vend + threadIdx.x;
+  }
+  for (uint64_t i = tail; i < end; i += FA_BLOCK) {
+    uint16_t* p0 = const_cast<uint16_t*>(static_cast<const uint16_t*>(a.p[0][l]));
+    if constexpr (OP == 0) {
+      f16[i] = p0[i];
+    } else if constexpr (OP == 2) {
+      uint16_t acc = seg16_first<K>(p0[i], cf[0]);
+      for (int j = 1; j < a.nlists; ++j) acc = seg16_next<K>(acc, static_cast<const uint16_t*>(a.p[j][l])[i], cf[j]);
+      f16[i] = acc;
+    } else {
+      if constexpr (FLAT32) p0[i] = seg16_inc32<K>(p0[i], f32[i], cf[0], twice);
+      else p0[i] = seg16_inc<K>(p0[i], f16[i], cf[0]);
+    }
+  }
+}
+
+// Launch of the 16-bit forms: ``layer_kind`` is the kind of every list (the public entries
+// reject mixed lists before they come here), ``flat_kind`` that kind or, for the increment of a
+// bf16 model, FEDAGG_F32.
+static bool is_16bit_kind(int k) { return k == FEDAGG_F16 || k == FEDAGG_BF16; }
+
+template <int OP>
+int flat_seg16_launch(const void* const* ptrs, int layer_kind, int nlists, const double* coeffs,
+                      const uint64_t* numel, int L, void* flat, int flat_kind, hipStream_t s) {
+  if (L < 0 || nlists < 1 || nlists > FEDAGG_FLAT_MAX_LISTS || (L > 0 && (!ptrs || !numel || !flat)))
+    return fail(FEDAGG_EINVAL, "flat op: invalid argument (L=%lld)", L);
+  const bool flat32 = OP == 3 && layer_kind == FEDAGG_BF16 && flat_kind == FEDAGG_F32;
+  if ((layer_kind != FEDAGG_F16 && layer_kind != FEDAGG_BF16) || (flat_kind != layer_kind && !flat32))
+    return fail(FEDAGG_EINVAL, "flat op: unsupported 16-bit kinds (flat kind %lld)", flat_kind);
+  if ((reinterpret_cast<uintptr_t>(flat) & (flat32 ? 3u : 1u)) != 0)
+    return fail(FEDAGG_EINVAL, "flat op: misaligned flat bucket");
+  uint64_t off = 0;
+  for (int l0 = 0; l0 < L; l0 += SEG_GROUP) {
+    const int nl = (L - l0) < SEG_GROUP ? (L - l0) : SEG_GROUP;
+    SegArgs a;
+    memset(&a, 0, sizeof(a));
+    a.nl = nl;
+    a.nlists = nlists;
+    for (int j = 0; j < nlists; ++j) a.coeff[j] = coeffs ? coeffs[j] : 1.0;
+    uint64_t blocks = 0;
+    for (int l = 0; l < nl; ++l) {
+      for (int j = 0; j < nlists; ++j) {
+        a.p[j][l] = ptrs[(size_t)j * L + l0 + l];
+        if (!a.p[j][l] && numel[l0 + l]) return fail(FEDAGG_EINVAL, "flat op: NULL layer pointer %lld", l0 + l);
+        if (reinterpret_cast<uintptr_t>(a.p[j][l]) & 1u)
+          return fail(FEDAGG_EINVAL, "flat op: misaligned layer pointer %lld", l0 + l);
+      }
+      a.n[l] = numel[l0 + l];
+      a.flat_off[l] = off;
+      a.block_start[l] = (uint32_t)blocks;
+      off += numel[l0 + l];
+      blocks += (numel[l0 + l] + SEG_CHUNK - 1) / SEG_CHUNK;
+    }
+    a.block_start[nl] = (uint32_t)blocks;
+    if (blocks == 0) continue;
+    const dim3 g((unsigned)blocks), b(FA_BLOCK);
+    if constexpr (OP == 0) {  // a copy of bit patterns: one instance serves both kinds
+      hipLaunchKernelGGL((flat_seg16_kernel<0, FEDAGG_F16, false>), g, b, 0, s, a, flat, g_flat_vec);
+    } else {
+      if (flat32) {
+        if constexpr (OP == 3)
+          hipLaunchKernelGGL((flat_seg16_kernel<3, FEDAGG_BF16, true>), g, b, 0, s, a, flat, g_flat_vec);
+      } else if (layer_kind == FEDAGG_F16) {
+        hipLaunchKernelGGL((flat_seg16_kernel<OP, FEDAGG_F16, false>), g, b, 0, s, a, flat, g_flat_vec);
+      } else {
+        hipLaunchKernelGGL((flat_seg16_kernel<OP, FEDAGG_BF16, false>), g, b, 0, s, a, flat, g_flat_vec);
+      }
+    }
+    int rc = check_launch("flat_seg16_kernel");
+    if (rc) return rc;
+  }
+  return FEDAGG_OK;
+}
+
+// ------------------------------------------------------------------------------------
 // read-stream probe (same 16-B non-temporal load path as the bucket kernels)
 // ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FA_BLOCK) read_probe_kernel(const float* __restrict__ x, uint64_t nvec,
@@ -2743,11 +2980,33 @@ int fedagg_flat_increment_f32(float* const* d_layers, const uint64_t* numel, int
 }
 int fedagg_flat_gather(const void* const* d_layers, int kind, const uint64_t* numel, int L, void* d_flat,
                        void* stream) {
+  if (is_16bit_kind(kind))
+    return flat_seg16_launch<0>(d_layers, kind, 1, nullptr, numel, L, d_flat, kind, (hipStream_t)stream);
   return flat_seg_launch<0>(d_layers, &kind, 1, nullptr, numel, L, d_flat, kind, (hipStream_t)stream);
 }
 int fedagg_flat_wsum(const void* const* d_layers, const int* kinds, int nlists, const double* coeffs,
                      const uint64_t* numel, int L, void* d_flat, int flat_kind, void* stream) {
+  if (kinds && nlists >= 1 && nlists <= FEDAGG_FLAT_MAX_LISTS) {
+    bool any16 = is_16bit_kind(flat_kind);
+    for (int j = 0; j < nlists; ++j) any16 = any16 || is_16bit_kind(kinds[j]);
+    if (any16) {  // every list and the result of ONE 16-bit kind; torch's promotion is not done here
+      for (int j = 0; j < nlists; ++j)
+        if (kinds[j] != flat_kind)
+          return fail(FEDAGG_EINVAL, "flat wsum: 16-bit lists take lists and a result of one kind (list %lld)", j);
+      return flat_seg16_launch<2>(d_layers, flat_kind, nlists, coeffs, numel, L, d_flat, flat_kind,
+                                  (hipStream_t)stream);
+    }
+  }
   return flat_seg_launch<2>(d_layers, kinds, nlists, coeffs, numel, L, d_flat, flat_kind, (hipStream_t)stream);
+}
+int fedagg_flat_increment_kind(void* const* d_layers, int layer_kind, const uint64_t* numel, int L,
+                               const void* d_flat, int flat_kind, double multiplier, void* stream) {
+  const bool ok = (layer_kind == FEDAGG_F16 && flat_kind == FEDAGG_F16) ||
+                  (layer_kind == FEDAGG_BF16 && (flat_kind == FEDAGG_BF16 || flat_kind == FEDAGG_F32));
+  if (!ok)
+    return fail(FEDAGG_EINVAL, "flat increment: unsupported (layer, flat) kinds (flat kind %lld)", flat_kind);
+  return flat_seg16_launch<3>(reinterpret_cast<const void* const*>(d_layers), layer_kind, 1, &multiplier, numel, L,
+                              const_cast<void*>(d_flat), flat_kind, (hipStream_t)stream);
 }
 int fedagg_flat_increment(float* const* d_layers, const uint64_t* numel, int L, const void* d_flat, int flat_kind,
                           double multiplier, void* stream) {

@@ -37,9 +37,10 @@ import numpy as np
 
 from . import _native, handoff, runtime
 from .layout import BucketLayout
-from .wire import flat_of
+from .wire import BF16, flat_of
 
 KINDS = ("f32", "bf16", "f64", "f16")
+BF16_GROUP = "bf16"  # fedavg()'s dtype-group key of wire.BF16 layers (the others are NumPy dtype strings)
 
 # GPU selection of the strategies (resolve_devices): an index, several indices, or "all"
 Devices = Optional[Union[int, Sequence[int], str]]
@@ -67,6 +68,8 @@ def torch_dtype(kind_or_np):
 
 def kind_of(np_dtype) -> str:
     d = np.dtype(np_dtype)
+    if d == BF16:
+        return "bf16"
     if d == np.float32:
         return "f32"
     if d == np.float64:
@@ -74,6 +77,16 @@ def kind_of(np_dtype) -> str:
     if d == np.float16:
         return "f16"
     raise NotImplementedError(f"no aggregation kernel for dtype {d}")
+
+
+def reject_bf16(rows, what: str) -> None:
+    """``wire.BF16`` layers hold bit patterns: a path with no bf16 kernel refuses them instead of
+    computing on the patterns."""
+    for row in rows:
+        for a in row:
+            if getattr(a, "dtype", None) == BF16:
+                raise NotImplementedError(f"{what}: no bf16 path for wire.BF16 layers "
+                                          "(FedAvg on one GPU aggregates them)")
 
 
 def native_byte_order(rows):
@@ -772,6 +785,15 @@ class AggregationEngine:
         # group layers by (result dtype, per-client product dtypes): NumPy promotion per layer
         groups: Dict[Tuple, List[int]] = {}
         for li in range(L):
+            # wire.BF16 first: NumPy has no promotion for it (np.result_type raises)
+            n_bf16 = sum(1 for pu in parameters_updates if pu[li].dtype == BF16)
+            if n_bf16 == K:
+                groups.setdefault((BF16_GROUP, None), []).append(li)
+                continue
+            if n_bf16:
+                other = next(pu[li].dtype for pu in parameters_updates if pu[li].dtype != BF16)
+                raise NotImplementedError(f"FedAvg engine: layer {li} is wire.BF16 for {n_bf16} of {K} clients and "
+                                          f"{other} for the others; one dtype per layer when bf16 is involved")
             pds = tuple(np.result_type(pu[li].dtype, 1.0) for pu in parameters_updates)
             for d in pds:
                 if d not in (np.float16, np.float32, np.float64):
@@ -782,10 +804,15 @@ class AggregationEngine:
 
         if len(groups) == 1:
             (rstr, mixed), = groups.keys()
-            R = np.dtype(rstr)
+            R = BF16 if rstr == BF16_GROUP else np.dtype(rstr)
             direct = mixed is None and all(a.dtype == R for pu in parameters_updates for a in pu)
-            need = (K + 1) * BucketLayout(range(L), [a.shape for a in parameters_updates[0]], R).ld * R.itemsize
+            # (bf16 rows are 2-byte, their fp32 result counts as two more rows)
+            need = (K + (2 if R == BF16 else 1)) * BucketLayout(range(L), [a.shape for a in parameters_updates[0]],
+                                                                 R).ld * R.itemsize
             ooc = self._out_of_core(need, (self._B_BUCKET, self._B_OUT, self._B_WS)) if direct else None
+            if ooc is not None and R == BF16:
+                raise NotImplementedError("FedAvg engine: the out-of-core path has no bf16 path for wire.BF16 layers "
+                                          f"({need} bytes do not fit the bucket budget)")
             if ooc is not None:
                 out = ooc.fedavg(parameters_updates, n_samples, wire)
                 self.last_timing = {"out_of_core": ooc.last_timing, "staging": "out-of-core"}
@@ -794,7 +821,9 @@ class AggregationEngine:
         if len(groups) != 1:
             self._prestaged = {}
         for (rstr, mixed), layer_ids in groups.items():
-            R = np.dtype(rstr)
+            # R: the rows' dtype; Rout: the result's (bf16 rows average into fp32)
+            R = BF16 if rstr == BF16_GROUP else np.dtype(rstr)
+            Rout = np.dtype(np.float32) if R == BF16 else R
             kind = kind_of(R)
             layout = BucketLayout(layer_ids, [parameters_updates[0][li].shape for li in layer_ids], R)
             rows = [[pu[li] for li in layer_ids] for pu in parameters_updates]
@@ -814,14 +843,14 @@ class AggregationEngine:
             tv = st.tv
             tm["stage_s"] = tm.get("stage_s", 0.0) + time.perf_counter() - t0
             tm["layout"] = "tiles" if tv is not None else "rows"
-            d_out = s.buffer(self._B_OUT, layout.ld * R.itemsize)
+            d_out = s.buffer(self._B_OUT, layout.ld * Rout.itemsize)
             ws = s.buffer(self._B_WS, _native.load().fedagg_pairwise_ws_bytes(K, layout.pairwise_idx.size, 8))
             t1 = time.perf_counter()
             if tv is not None:
                 TiledFedAvgPlan(kind, st.base, K, w, layout.M, d_out, layout.pairwise_idx, ws, tv).launch(s.stream)
             else:
                 FedAvgPlan(kind, st.ptrs, w, layout.M, d_out, layout.pairwise_idx, ws).launch(s.stream)
-            out = runtime.reusable_host_array(layout.M, R, f"fedavg{'-mixed' if mixed else ''}")
+            out = runtime.reusable_host_array(layout.M, Rout, f"fedavg{'-mixed' if mixed else ''}")
             s.fetch(d_out, out)  # stream-ordered after the kernel; returns when the data is home
             self._handoff_keep = None  # the kernel is done with the clients' buckets
             if len(groups) == 1:
@@ -857,6 +886,7 @@ class AggregationEngine:
         K, L = len(rows), len(rows[0])
         if L == 0:
             return []
+        reject_bf16(rows, "sequential_sum")
         pdt = []
         for row in rows:
             ds = {np.result_type(a.dtype, 1.0) for a in row}
@@ -955,6 +985,7 @@ class AggregationEngine:
             return 0, [], []
         lists = (parameters_updates, control_variate_updates, server_control_variates)
         for lst in lists:
+            reject_bf16(lst, "Scaffold engine")
             for client in lst:
                 for a in client:
                     if a.dtype.kind not in "biuf" or a.dtype == np.longdouble:

@@ -35,8 +35,8 @@ import numpy as np
 
 from . import _native, runtime
 from .engine import (TILED_KINDS, AggregationEngine, FedAvgPlan, ScaffoldPlan, TiledFedAvgPlan, direct_rows,
-                     equal_count, fedavg_weights, kind_of, native_byte_order, scaffold_weights, serialized,
-                     tiled_elems, tiled_recommended, tiled_tile)
+                     equal_count, fedavg_weights, kind_of, native_byte_order, reject_bf16, scaffold_weights,
+                     serialized, tiled_elems, tiled_recommended, tiled_tile)
 from .layout import ROW_ALIGN_BYTES, BucketLayout
 from .sharding import SHARD_ALIGN, shard_bounds
 
@@ -288,6 +288,7 @@ class MultiDeviceEngine:
         L = len(parameters_updates[0])
         if L == 0:
             return []
+        reject_bf16(parameters_updates, "MultiDeviceEngine.fedavg")
         dts = {a.dtype for pu in parameters_updates for a in pu}
         R = np.result_type(next(iter(dts)), 1.0) if len(dts) == 1 else None
         if R is None or R != next(iter(dts)) or R not in (np.float16, np.float32, np.float64):

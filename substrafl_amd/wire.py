@@ -29,6 +29,35 @@ import numpy as np
 
 _SMALL = 4096  # below this a payload is copied on load (never alias a possibly shared bytes object)
 
+# Host representation of bfloat16 (NumPy has none): a 2-byte structured dtype holding the bit
+# pattern.  NumPy refuses arithmetic and promotion on it (``a * 0.5``, ``a + a``, ``np.sum``,
+# ``np.result_type(BF16, 1.0)`` raise), so code that does not know the dtype fails loudly instead
+# of averaging bit patterns; it pickles with plain NumPy and stays an ``np.ndarray``.
+BF16 = np.dtype([("bfloat16", "<u2")])
+
+
+def is_bf16(a) -> bool:
+    """Whether ``a`` (an array or a dtype) has the :data:`BF16` host dtype."""
+    return getattr(a, "dtype", a) == BF16
+
+
+def bf16_to_float32(a) -> np.ndarray:
+    """The exact fp32 values of a :data:`BF16` array (same shape)."""
+    a = np.asarray(a)
+    if a.dtype != BF16:
+        raise TypeError(f"bf16_to_float32: expected dtype wire.BF16, got {a.dtype}")
+    return (a["bfloat16"].astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
+def float32_to_bf16(a) -> np.ndarray:
+    """``a`` (cast to fp32) rounded to bfloat16 as a :data:`BF16` array of the same shape: round
+    to nearest even, overflow to +-inf, NaN stays NaN (quiet, payload truncated)."""
+    u = np.asarray(a, dtype=np.float32).view(np.uint32)
+    r = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    r = np.where(nan, (u >> np.uint32(16)) | np.uint32(0x0040), r).astype(np.uint16)
+    return r.view(BF16)
+
 
 class _Bucket:
     """Owner of one flat byte buffer (1-D uint8, C-contiguous, writable)."""
@@ -83,14 +112,16 @@ class BucketArray(np.ndarray):
     def __reduce_ex__(self, protocol):
         if self._bucket is None:
             return self.view(np.ndarray).__reduce_ex__(protocol)
-        return _layer, (self._bucket, self._offset, self.shape, self.dtype.str)
+        # a structured dtype's ``str`` is "|V2" and loses its field (wire.BF16): those carry ``descr``
+        dt = self.dtype.str if self.dtype.names is None else self.dtype.descr
+        return _layer, (self._bucket, self._offset, self.shape, dt)
 
     def __reduce__(self):
         return self.__reduce_ex__(2)
 
 
-def _layer(bucket: _Bucket, offset: int, shape: Tuple[int, ...], dtype: str) -> BucketArray:
-    dt = np.dtype(dtype)
+def _layer(bucket: _Bucket, offset: int, shape: Tuple[int, ...], dtype) -> BucketArray:
+    dt = np.dtype([tuple(f) for f in dtype] if isinstance(dtype, list) else dtype)
     n = int(np.prod(shape, dtype=np.int64)) if len(shape) else 1
     return _member(bucket, offset, dt, n, tuple(shape))
 
