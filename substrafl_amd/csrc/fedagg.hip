@@ -1,5 +1,6 @@
 // fedagg.hip -- hand-written gfx950 (MI355X / CDNA4) kernels for SubstraFL's aggregation
-// hot path, behind the C ABI declared in include/fedagg.h.
+// hot path, behind the C ABI declared in include/fedagg.h.  (The client-side flat-bucket ops,
+// fedagg_flat_*, are in flat_ops.hip; fedagg_internal.h is what the translation units share.)
 //
 // The path is element-wise and HBM-bound (0.5 FLOP per input byte for fp32 FedAvg), so
 // the design is a pure streaming one -- no MFMA, no LDS staging of the client streams:
@@ -25,15 +26,13 @@
 
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
 #include <vector>
 
-#include "fedagg.h"
+#include "fedagg_internal.h"
 
 // FEDAGG_TUNING=1 (`__graft_entry__.build(tuning=True)`, tools/): every launch variant the
 // experiment knobs of fedagg_tune select is instantiated -- the shapes, load paths, occupancy caps
@@ -44,26 +43,14 @@
 #define FEDAGG_TUNING 0
 #endif
 
-#define FA_BLOCK 256
 #define FA_UNROLL 8
+
+using fedagg_internal::check_launch;
+using fedagg_internal::fail;
 
 namespace {
 
 thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, long long b = 0) {
-  snprintf(g_err, sizeof(g_err), fmt, b);
-  return code;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return FEDAGG_EHIP;
-  }
-  return FEDAGG_OK;
-}
 
 // Launch shape (fedagg_tune); defaults are the values measured best on MI355X.
 int g_grid_cap = 0;     // workgroups per launch before grid-striding (0: one step per workgroup)
@@ -81,7 +68,7 @@ int g_buf = 0;          // FedAvg: buffer-descriptor client loads (8/16-KiB tile
 int g_fa_occ = 0;       // FedAvg: register-capped occupancy variants (0: off; 2-4 with the 8/16-KiB shapes)
 int g_sc_buf = 0;       // Scaffold: buffer-descriptor client loads (fp32 inputs, 4- and 8-vector tiles)
 int g_sc_bsplit = 0;    // Scaffold: bucket-split workgroup pairs (delta / control variate per workgroup)
-int g_flat_vec = 1;     // 16-B (4-element) client flat ops when every operand is fp32
+int g_flat_vec = 1;     // 16-B accesses in the client flat ops (flat_ops.hip, through fedagg_internal::flat_vec)
 int g_eq_vec = 1;       // vectorised c-equality check (16-B loads) when every copy is 16-B aligned
 int g_sc_pipe = 0;      // Scaffold: software-pipelined client groups (next group's loads before this group's adds)
 int g_tpb = 1;          // consecutive tiles per workgroup (1: one step per workgroup)
@@ -1503,442 +1490,6 @@ __global__ void __launch_bounds__(FA_BLOCK)
 }
 
 // ------------------------------------------------------------------------------------
-// Client-side flat-bucket ops: the producer / consumer of the
-// buckets, i.e. weight_manager's per-layer torch loops (weight_manager.py:103-238) done as one
-// launch over up to SEG_GROUP layers.  Workgroup b serves layer l with
-// block_start[l] <= b < block_start[l+1], elements [(b - block_start[l]) * SEG_CHUNK, ...).
-// Semantics follow the reference's torch ops bit for bit:
-//   weighted_sum_parameters (:182-212): Python sum() from int 0 over param * coeff, i.e.
-//     acc = fl(0 + fl(x_0 * fl32(c_0))); acc = fl(acc + fl(x_i * fl32(c_i)))  (-0 becomes +0)
-//   increment_parameters (:103-137):  w = fl(w + fl(fl32(mult) * u))
-//   get_parameters / set_parameters: plain copies.
-// ------------------------------------------------------------------------------------
-#define SEG_GROUP 32
-#define SEG_CHUNK 8192  // elements per workgroup
-
-struct SegArgs {
-  const void* p[FEDAGG_FLAT_MAX_LISTS][SEG_GROUP];  // list-major layer pointers
-  uint64_t n[SEG_GROUP];
-  uint64_t flat_off[SEG_GROUP];
-  uint32_t block_start[SEG_GROUP + 1];
-  double coeff[FEDAGG_FLAT_MAX_LISTS];
-  uint32_t f64;  // bit j: list j is fp64; bit 31: the flat bucket is fp64
-  int nl, nlists;
-};
-
-__device__ __forceinline__ int seg_of_block(const SegArgs& a, uint32_t b) {
-  int l = 0;
-  while (l + 1 < a.nl && a.block_start[l + 1] <= b) ++l;  // scalar, <= SEG_GROUP steps
-  return l;
-}
-
-// torch's ``tensor * python_float``: fp32 tensors compute in fp32 with the scalar rounded to
-// fp32, fp64 tensors in fp64.  Returned in double (exact for the fp32 product).
-__device__ __forceinline__ double seg_product(const void* p, uint64_t i, bool is64, double c) {
-#pragma clang fp contract(off)
-  if (is64) return static_cast<const double*>(p)[i] * c;
-  return (double)(static_cast<const float*>(p)[i] * (float)c);
-}
-
-// op 0: gather (flat = p0), 1: scatter (p0 = flat), 2: wsum (flat = sum() of p_j * c_j),
-// 3: increment (p0 = p0 + c0 * flat).  Layers and flat are fp32 or fp64 per SegArgs::f64;
-// mixed fp32/fp64 operands follow torch's promotion (the op runs in fp64 once either side is).
-template <int OP>
-__global__ void __launch_bounds__(FA_BLOCK) flat_seg_kernel(const SegArgs a, void* __restrict__ flat) {
-#pragma clang fp contract(off)
-  const int l = seg_of_block(a, blockIdx.x);
-  const uint64_t base = (uint64_t)(blockIdx.x - a.block_start[l]) * SEG_CHUNK;
-  const uint64_t n = a.n[l];
-  const bool flat64 = (a.f64 >> 31) & 1u;
-  float* f32 = static_cast<float*>(flat) + a.flat_off[l];
-  double* f64 = static_cast<double*>(flat) + a.flat_off[l];
-  for (uint64_t i = base + threadIdx.x; i < base + SEG_CHUNK && i < n; i += FA_BLOCK) {
-    if constexpr (OP == 0) {
-      if (flat64) f64[i] = static_cast<const double*>(a.p[0][l])[i];
-      else f32[i] = static_cast<const float*>(a.p[0][l])[i];
-    } else if constexpr (OP == 1) {
-      if (flat64) const_cast<double*>(static_cast<const double*>(a.p[0][l]))[i] = f64[i];
-      else const_cast<float*>(static_cast<const float*>(a.p[0][l]))[i] = f32[i];
-    } else if constexpr (OP == 2) {
-      // Python sum() from int 0: 0 + p_0 (-0 becomes +0), then acc + p_j in the promoted type
-      bool acc64 = a.f64 & 1u;
-      double acc = seg_product(a.p[0][l], i, acc64, a.coeff[0]);
-      acc = acc64 ? 0.0 + acc : (double)(0.0f + (float)acc);
-      for (int j = 1; j < a.nlists; ++j) {
-        const bool is64 = (a.f64 >> j) & 1u;
-        const double t = seg_product(a.p[j][l], i, is64, a.coeff[j]);
-        acc64 = acc64 || is64;
-        acc = acc64 ? acc + t : (double)((float)acc + (float)t);
-      }
-      if (flat64) f64[i] = acc;
-      else f32[i] = (float)acc;
-    } else {
-      // w += m * u with w fp32: u fp32 -> fl32(w + fl32(fl32(m) * u)); u fp64 -> fl32(w + fl64(m * u))
-      float* w = const_cast<float*>(static_cast<const float*>(a.p[0][l]));
-      if (flat64) {
-        const double t = a.coeff[0] * f64[i];
-        w[i] = (float)((double)w[i] + t);
-      } else {
-        const float t = (float)a.coeff[0] * f32[i];
-        w[i] = w[i] + t;
-      }
-    }
-  }
-}
-
-// All-fp32 form of flat_seg_kernel: 16-B accesses (4 elements per lane).  Layer tensors are
-// 16-B aligned, but a layer's slice of the flat bucket starts wherever the previous layers end,
-// so the accesses are declared 4-B aligned: gfx950 serves unaligned dwordx4 loads and stores,
-// a wave still touches one contiguous KiB (plus at most one extra line).  Same per-element
-// arithmetic as the scalar kernel's fp32 branches.
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
-
-template <int OP>
-__global__ void __launch_bounds__(FA_BLOCK) flat_seg_vec_kernel(const SegArgs a, float* __restrict__ flat) {
-#pragma clang fp contract(off)
-  const int l = seg_of_block(a, blockIdx.x);
-  const uint64_t base = (uint64_t)(blockIdx.x - a.block_start[l]) * SEG_CHUNK;
-  const uint64_t n = a.n[l];
-  const uint64_t end = base + SEG_CHUNK < n ? base + SEG_CHUNK : n;
-  float* f = flat + a.flat_off[l];
-  float cf[FEDAGG_FLAT_MAX_LISTS];
-#pragma unroll
-  for (int j = 0; j < FEDAGG_FLAT_MAX_LISTS; ++j) cf[j] = (float)a.coeff[j];  // torch rounds the scalar
-  for (uint64_t i = base + 4 * (uint64_t)threadIdx.x; i < end; i += 4 * (uint64_t)FA_BLOCK) {
-    if (i + 4 <= end) {
-      if constexpr (OP == 0) {
-        *reinterpret_cast<f32x4u*>(f + i) = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(a.p[0][l]) + i);
-      } else if constexpr (OP == 1) {
-        *reinterpret_cast<f32x4u*>(const_cast<float*>(static_cast<const float*>(a.p[0][l])) + i) =
-            *reinterpret_cast<const f32x4u*>(f + i);
-      } else if constexpr (OP == 2) {
-        const f32x4u t0 = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(a.p[0][l]) + i) * cf[0];
-        f32x4u acc = f32x4u(0.0f) + t0;  // Python sum() starts from int 0
-        for (int j = 1; j < a.nlists; ++j) {
-          const f32x4u t = *reinterpret_cast<const f32x4u*>(static_cast<const float*>(a.p[j][l]) + i) * cf[j];
-          acc = acc + t;
-        }
-        *reinterpret_cast<f32x4u*>(f + i) = acc;
-      } else {
-        float* w = const_cast<float*>(static_cast<const float*>(a.p[0][l])) + i;
-        const f32x4u t = cf[0] * *reinterpret_cast<const f32x4u*>(f + i);
-        *reinterpret_cast<f32x4u*>(w) = *reinterpret_cast<const f32x4u*>(w) + t;
-      }
-    } else {
-      for (uint64_t e = i; e < end; ++e) {
-        if constexpr (OP == 0) {
-          f[e] = static_cast<const float*>(a.p[0][l])[e];
-        } else if constexpr (OP == 1) {
-          const_cast<float*>(static_cast<const float*>(a.p[0][l]))[e] = f[e];
-        } else if constexpr (OP == 2) {
-          float acc = 0.0f + static_cast<const float*>(a.p[0][l])[e] * cf[0];
-          for (int j = 1; j < a.nlists; ++j) {
-            const float t = static_cast<const float*>(a.p[j][l])[e] * cf[j];
-            acc = acc + t;
-          }
-          f[e] = acc;
-        } else {
-          float* w = const_cast<float*>(static_cast<const float*>(a.p[0][l]));
-          const float t = cf[0] * f[e];
-          w[e] = w[e] + t;
-        }
-      }
-    }
-  }
-}
-
-template <int OP>
-int flat_seg_launch(const void* const* ptrs, const int* kinds, int nlists, const double* coeffs,
-                    const uint64_t* numel, int L, void* flat, int flat_kind, hipStream_t s) {
-  if (L < 0 || nlists < 1 || nlists > FEDAGG_FLAT_MAX_LISTS || (L > 0 && (!ptrs || !numel || !flat)))
-    return fail(FEDAGG_EINVAL, "flat op: invalid argument (L=%lld)", L);
-  if (flat_kind != FEDAGG_F32 && flat_kind != FEDAGG_F64)
-    return fail(FEDAGG_EINVAL, "flat op: the flat bucket must be fp32 or fp64 (kind %lld)", flat_kind);
-  uint32_t mask = flat_kind == FEDAGG_F64 ? (1u << 31) : 0u;
-  bool any64 = false;
-  for (int j = 0; j < nlists; ++j) {
-    const int k = kinds ? kinds[j] : FEDAGG_F32;
-    if (k != FEDAGG_F32 && k != FEDAGG_F64) return fail(FEDAGG_EINVAL, "flat op: list %lld is not fp32/fp64", j);
-    if (k == FEDAGG_F64) mask |= 1u << j, any64 = true;
-  }
-  // operand kinds each op supports (the Python layer routes everything else to torch)
-  if ((OP == 0 || OP == 1) && any64 != (flat_kind == FEDAGG_F64))
-    return fail(FEDAGG_EINVAL, "flat copy: layer and flat kinds differ");
-  if (OP == 2 && any64 != (flat_kind == FEDAGG_F64))
-    return fail(FEDAGG_EINVAL, "flat wsum: the result kind must be the promoted kind of the lists");
-  if (OP == 3 && any64) return fail(FEDAGG_EINVAL, "flat increment: parameters must be fp32");
-  uint64_t off = 0;
-  for (int l0 = 0; l0 < L; l0 += SEG_GROUP) {
-    const int nl = (L - l0) < SEG_GROUP ? (L - l0) : SEG_GROUP;
-    SegArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nl = nl;
-    a.nlists = nlists;
-    a.f64 = mask;
-    for (int j = 0; j < nlists; ++j) a.coeff[j] = coeffs ? coeffs[j] : 1.0;
-    uint64_t blocks = 0;
-    for (int l = 0; l < nl; ++l) {
-      for (int j = 0; j < nlists; ++j) {
-        a.p[j][l] = ptrs[(size_t)j * L + l0 + l];
-        if (!a.p[j][l] && numel[l0 + l]) return fail(FEDAGG_EINVAL, "flat op: NULL layer pointer %lld", l0 + l);
-      }
-      a.n[l] = numel[l0 + l];
-      a.flat_off[l] = off;
-      a.block_start[l] = (uint32_t)blocks;
-      off += numel[l0 + l];
-      blocks += (numel[l0 + l] + SEG_CHUNK - 1) / SEG_CHUNK;
-    }
-    a.block_start[nl] = (uint32_t)blocks;
-    if (blocks == 0) continue;
-    if (mask == 0 && g_flat_vec)
-      hipLaunchKernelGGL((flat_seg_vec_kernel<OP>), dim3((unsigned)blocks), dim3(FA_BLOCK), 0, s, a,
-                         static_cast<float*>(flat));
-    else
-      hipLaunchKernelGGL((flat_seg_kernel<OP>), dim3((unsigned)blocks), dim3(FA_BLOCK), 0, s, a, flat);
-    int rc = check_launch("flat_seg_kernel");
-    if (rc) return rc;
-  }
-  return FEDAGG_OK;
-}
-
-// ------------------------------------------------------------------------------------
-// 16-bit kinds of the client flat ops (fp16 and bf16 models).  torch's arithmetic for these
-// dtypes: every op computes in fp32 (opmath) and rounds its result once to the tensor's type, a
-// Python scalar is rounded to fp32.  K is the 16-bit kind (elements handled as their bit
-// patterns), FLAT32 says the flat bucket is fp32 (increment of a bf16 model by the engine's fp32
-// average: the promoted in-place add, w = bf16(fl32(w) + fl32(fl32(m) * u)), with the update
-// rounded to bf16 first in a layer's leading full 16384-element blocks, see seg16_inc32).
-//   wsum:      p_j = fl_K(fl32(x_j) * fl32(c_j)); acc = fl_K(0.0f + p_0); acc = fl_K(acc + p_j)
-//   increment: w = fl_K(fl32(w) + fl32(fl_K(fl32(m) * fl32(u))))
-// ------------------------------------------------------------------------------------
-template <int K>
-__device__ __forceinline__ float h16_to_f32(uint16_t b) {
-  if constexpr (K == FEDAGG_F16) return (float)__builtin_bit_cast(_Float16, b);
-  else return __uint_as_float((uint32_t)b << 16);
-}
-
-// fp32 -> 16 bits, round to nearest even, overflow to +-inf, NaN stays NaN (quiet bit set)
-template <int K>
-__device__ __forceinline__ uint16_t f32_to_h16(float f) {
-  if constexpr (K == FEDAGG_F16) {
-    // The fp32 value and the converted bits each pass through a register of their own, so the
-    // rounding is one plain v_cvt_f16_f32 of the fp32 result: the compiler neither folds the
-    // multiply before it into a mixed-precision fma nor pairs two conversions into a packed one.
-    asm("" : "+v"(f));
-    uint32_t r = __builtin_bit_cast(uint16_t, (_Float16)f);
-    asm("" : "+v"(r));
-    return (uint16_t)r;
-  } else {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x0040u);
-    return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
-  }
-}
-
-struct H8 {
-  uint16_t v[8];
-};
-struct F8 {
-  float v[8];
-};
-typedef uint32_t u32x4a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ H8 h8_unpack(const u32x4 r) {
-  H8 o;
-  o.v[0] = (uint16_t)r.x, o.v[1] = (uint16_t)(r.x >> 16), o.v[2] = (uint16_t)r.y, o.v[3] = (uint16_t)(r.y >> 16);
-  o.v[4] = (uint16_t)r.z, o.v[5] = (uint16_t)(r.z >> 16), o.v[6] = (uint16_t)r.w, o.v[7] = (uint16_t)(r.w >> 16);
-  return o;
-}
-__device__ __forceinline__ u32x4 h8_pack(const H8& h) {
-  u32x4 r;
-  r.x = h.v[0] | ((uint32_t)h.v[1] << 16), r.y = h.v[2] | ((uint32_t)h.v[3] << 16);
-  r.z = h.v[4] | ((uint32_t)h.v[5] << 16), r.w = h.v[6] | ((uint32_t)h.v[7] << 16);
-  return r;
-}
-// 8 elements at p: a 16-B aligned layer, or (h8_*_a4) a 4-B aligned slice of the flat bucket --
-// the access the fp32 form uses for its slice.  There is no form for a 2-B aligned address:
-// eight 2-byte accesses of one lane would be merged into one wide access by the compiler.
-__device__ __forceinline__ H8 h8_load(const uint16_t* p) { return h8_unpack(*reinterpret_cast<const u32x4*>(p)); }
-__device__ __forceinline__ H8 h8_load_a4(const uint16_t* p) {
-  return h8_unpack(*reinterpret_cast<const u32x4a4*>(p));
-}
-__device__ __forceinline__ void h8_store(uint16_t* p, const H8& h) { *reinterpret_cast<u32x4*>(p) = h8_pack(h); }
-__device__ __forceinline__ void h8_store_a4(uint16_t* p, const H8& h) {
-  *reinterpret_cast<u32x4a4*>(p) = h8_pack(h);
-}
-
-template <int K>
-__device__ __forceinline__ uint16_t seg16_first(uint16_t x, float c) {
-#pragma clang fp contract(off)
-  const uint16_t p = f32_to_h16<K>(h16_to_f32<K>(x) * c);
-  return f32_to_h16<K>(0.0f + h16_to_f32<K>(p));  // Python sum() starts from int 0: -0 becomes +0
-}
-template <int K>
-__device__ __forceinline__ uint16_t seg16_next(uint16_t acc, uint16_t x, float c) {
-#pragma clang fp contract(off)
-  const uint16_t p = f32_to_h16<K>(h16_to_f32<K>(x) * c);
-  return f32_to_h16<K>(h16_to_f32<K>(acc) + h16_to_f32<K>(p));
-}
-template <int K>
-__device__ __forceinline__ uint16_t seg16_inc(uint16_t w, uint16_t u, float m) {
-#pragma clang fp contract(off)
-  const uint16_t t = f32_to_h16<K>(m * h16_to_f32<K>(u));
-  return f32_to_h16<K>(h16_to_f32<K>(w) + h16_to_f32<K>(t));
-}
-// A 16-bit parameter plus fl32(m * u) with u fp32.  torch's type promotion defines the in-place
-// add as the fp32 sum rounded once, and that is what its CPU kernels and its generic device
-// kernel give.  torch on ROCm (2.10) serves an aligned contiguous ``bf16 += fp32`` with a
-// type-specialised vectorised kernel (ATen/native/cuda/CUDALoops.cuh, rt_binary_specializations
-// {BFloat16, BFloat16, float}) whose loads convert both inputs to the OUTPUT type: in every full
-// block of FLAT_TORCH_MIXED_BLOCK elements of the tensor the fp32 operand is rounded to bf16
-// before the add; the remainder of the tensor goes through the generic kernel.  The reference's
-// tensors are whole aligned allocations (one ``.to(device)`` per layer), so a layer's leading
-// full blocks get two roundings there, and ``twice`` reproduces that here.
-#define FLAT_TORCH_MIXED_BLOCK 16384  // vectorized_templated_config: 512 threads x 32 elements
-static_assert(FLAT_TORCH_MIXED_BLOCK % SEG_CHUNK == 0, "a chunk lies inside one torch block or outside all of them");
-template <int K>
-__device__ __forceinline__ uint16_t seg16_inc32(uint16_t w, float u, float m, bool twice) {
-#pragma clang fp contract(off)
-  float t = m * u;
-  if (twice) t = h16_to_f32<K>(f32_to_h16<K>(t));
-  return f32_to_h16<K>(h16_to_f32<K>(w) + t);
-}
-
-// op 0: gather, 2: wsum, 3: increment, over 16-bit layers (the ops of flat_seg_kernel).  With
-// ``vec`` a layer moves 8 elements per lane when its pointers are all 16-B aligned AND its slice
-// of a 16-bit flat bucket starts at an even element (4-B aligned): 16-B accesses on the layers,
-// the 4-B aligned 16-B access on the slice.  An fp32 flat bucket (FLAT32) is always 4-B aligned
-// and read with two such loads.  Every other layer -- a slice at an odd element offset never sees
-// a multi-dword access -- and the last < 8 elements of a chunk go element by element, one
-// 2-byte access per lane, consecutive lanes on consecutive elements.
-template <int OP, int K, bool FLAT32>
-__global__ void __launch_bounds__(FA_BLOCK) flat_seg16_kernel(const SegArgs a, void* __restrict__ flat, int vec) {
-#pragma clang fp contract(off)
-  const int l = seg_of_block(a, blockIdx.x);
-  const uint64_t base = (uint64_t)(blockIdx.x - a.block_start[l]) * SEG_CHUNK;
-  const uint64_t n = a.n[l];
-  const uint64_t end = base + SEG_CHUNK < n ? base + SEG_CHUNK : n;
-  uint16_t* f16 = static_cast<uint16_t*>(flat) + a.flat_off[l];
-  const float* f32 = static_cast<const float*>(flat) + a.flat_off[l];
-  float cf[FEDAGG_FLAT_MAX_LISTS];
-#pragma unroll
-  for (int j = 0; j < FEDAGG_FLAT_MAX_LISTS; ++j) cf[j] = (float)a.coeff[j];  // torch rounds the scalar
-  uintptr_t bits = 0;
-  for (int j = 0; j < a.nlists; ++j) bits |= reinterpret_cast<uintptr_t>(a.p[j][l]);
-  const bool wide = vec && (bits & 15u) == 0 && (FLAT32 || (reinterpret_cast<uintptr_t>(f16) & 3u) == 0);
-  // (BF16, F32) only: chunks inside the layer's leading full torch blocks (a block is two chunks)
-  const bool twice = base < (n & ~(uint64_t)(FLAT_TORCH_MIXED_BLOCK - 1));
-  uint64_t tail = base + threadIdx.x;  // where the element-by-element loop starts
-  if (wide) {
-    const uint64_t vend = base + ((end - base) & ~(uint64_t)7);
-    for (uint64_t i = base + 8 * (uint64_t)threadIdx.x; i < vend; i += 8 * (uint64_t)FA_BLOCK) {
-      uint16_t* p0 = const_cast<uint16_t*>(static_cast<const uint16_t*>(a.p[0][l])) + i;
-      if constexpr (OP == 0) {
-        h8_store_a4(f16 + i, h8_load(p0));
-      } else if constexpr (OP == 2) {
-        H8 x = h8_load(p0), acc;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc.v[e] = seg16_first<K>(x.v[e], cf[0]);
-        for (int j = 1; j < a.nlists; ++j) {
-          x = h8_load(static_cast<const uint16_t*>(a.p[j][l]) + i);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) acc.v[e] = seg16_next<K>(acc.v[e], x.v[e], cf[j]);
-        }
-        h8_store_a4(f16 + i, acc);
-      } else {
-        H8 w = h8_load(p0);
-        if constexpr (FLAT32) {
-          const f32x4u u0 = *reinterpret_cast<const f32x4u*>(f32 + i);
-          const f32x4u u1 = *reinterpret_cast<const f32x4u*>(f32 + i + 4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            w.v[e] = seg16_inc32<K>(w.v[e], u0[e], cf[0], twice);
-            w.v[e + 4] = seg16_inc32<K>(w.v[e + 4], u1[e], cf[0], twice);
-          }
-        } else {
-          const H8 u = h8_load_a4(f16 + i);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) w.v[e] = seg16_inc<K>(w.v[e], u.v[e], cf[0]);
-        }
-        h8_store(p0, w);
-      }
-    }
-    tail = vend + threadIdx.x;
-  }
-  for (uint64_t i = tail; i < end; i += FA_BLOCK) {
-    uint16_t* p0 = const_cast<uint16_t*>(static_cast<const uint16_t*>(a.p[0][l]));
-    if constexpr (OP == 0) {
-      f16[i] = p0[i];
-    } else if constexpr (OP == 2) {
-      uint16_t acc = seg16_first<K>(p0[i], cf[0]);
-      for (int j = 1; j < a.nlists; ++j) acc = seg16_next<K>(acc, static_cast<const uint16_t*>(a.p[j][l])[i], cf[j]);
-      f16[i] = acc;
-    } else {
-      if constexpr (FLAT32) p0[i] = seg16_inc32<K>(p0[i], f32[i], cf[0], twice);
-      else p0[i] = seg16_inc<K>(p0[i], f16[i], cf[0]);
-    }
-  }
-}
-
-// Launch of the 16-bit forms: ``layer_kind`` is the kind of every list (the public entries
-// reject mixed lists before they come here), ``flat_kind`` that kind or, for the increment of a
-// bf16 model, FEDAGG_F32.
-static bool is_16bit_kind(int k) { return k == FEDAGG_F16 || k == FEDAGG_BF16; }
-
-template <int OP>
-int flat_seg16_launch(const void* const* ptrs, int layer_kind, int nlists, const double* coeffs,
-                      const uint64_t* numel, int L, void* flat, int flat_kind, hipStream_t s) {
-  if (L < 0 || nlists < 1 || nlists > FEDAGG_FLAT_MAX_LISTS || (L > 0 && (!ptrs || !numel || !flat)))
-    return fail(FEDAGG_EINVAL, "flat op: invalid argument (L=%lld)", L);
-  const bool flat32 = OP == 3 && layer_kind == FEDAGG_BF16 && flat_kind == FEDAGG_F32;
-  if ((layer_kind != FEDAGG_F16 && layer_kind != FEDAGG_BF16) || (flat_kind != layer_kind && !flat32))
-    return fail(FEDAGG_EINVAL, "flat op: unsupported 16-bit kinds (flat kind %lld)", flat_kind);
-  if ((reinterpret_cast<uintptr_t>(flat) & (flat32 ? 3u : 1u)) != 0)
-    return fail(FEDAGG_EINVAL, "flat op: misaligned flat bucket");
-  uint64_t off = 0;
-  for (int l0 = 0; l0 < L; l0 += SEG_GROUP) {
-    const int nl = (L - l0) < SEG_GROUP ? (L - l0) : SEG_GROUP;
-    SegArgs a;
-    memset(&a, 0, sizeof(a));
-    a.nl = nl;
-    a.nlists = nlists;
-    for (int j = 0; j < nlists; ++j) a.coeff[j] = coeffs ? coeffs[j] : 1.0;
-    uint64_t blocks = 0;
-    for (int l = 0; l < nl; ++l) {
-      for (int j = 0; j < nlists; ++j) {
-        a.p[j][l] = ptrs[(size_t)j * L + l0 + l];
-        if (!a.p[j][l] && numel[l0 + l]) return fail(FEDAGG_EINVAL, "flat op: NULL layer pointer %lld", l0 + l);
-        if (reinterpret_cast<uintptr_t>(a.p[j][l]) & 1u)
-          return fail(FEDAGG_EINVAL, "flat op: misaligned layer pointer %lld", l0 + l);
-      }
-      a.n[l] = numel[l0 + l];
-      a.flat_off[l] = off;
-      a.block_start[l] = (uint32_t)blocks;
-      off += numel[l0 + l];
-      blocks += (numel[l0 + l] + SEG_CHUNK - 1) / SEG_CHUNK;
-    }
-    a.block_start[nl] = (uint32_t)blocks;
-    if (blocks == 0) continue;
-    const dim3 g((unsigned)blocks), b(FA_BLOCK);
-    if constexpr (OP == 0) {  // a copy of bit patterns: one instance serves both kinds
-      hipLaunchKernelGGL((flat_seg16_kernel<0, FEDAGG_F16, false>), g, b, 0, s, a, flat, g_flat_vec);
-    } else {
-      if (flat32) {
-        if constexpr (OP == 3)
-          hipLaunchKernelGGL((flat_seg16_kernel<3, FEDAGG_BF16, true>), g, b, 0, s, a, flat, g_flat_vec);
-      } else if (layer_kind == FEDAGG_F16) {
-        hipLaunchKernelGGL((flat_seg16_kernel<OP, FEDAGG_F16, false>), g, b, 0, s, a, flat, g_flat_vec);
-      } else {
-        hipLaunchKernelGGL((flat_seg16_kernel<OP, FEDAGG_BF16, false>), g, b, 0, s, a, flat, g_flat_vec);
-      }
-    }
-    int rc = check_launch("flat_seg16_kernel");
-    if (rc) return rc;
-  }
-  return FEDAGG_OK;
-}
-
-// ------------------------------------------------------------------------------------
 // read-stream probe (same 16-B non-temporal load path as the bucket kernels)
 // ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(FA_BLOCK) read_probe_kernel(const float* __restrict__ x, uint64_t nvec,
@@ -2838,6 +2389,19 @@ const T* cptr(const void* p) {
 
 namespace fedagg_internal {
 void set_error(const char* msg) { snprintf(g_err, sizeof(g_err), "%s", msg); }
+int fail(int code, const char* fmt, long long b) {
+  snprintf(g_err, sizeof(g_err), fmt, b);
+  return code;
+}
+int check_launch(const char* what) {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+    return FEDAGG_EHIP;
+  }
+  return FEDAGG_OK;
+}
+int flat_vec() { return g_flat_vec; }
 }  // namespace fedagg_internal
 
 // ======================================================================================
@@ -2957,61 +2521,6 @@ int fedagg_equal_count_f32(const float* const* d_copies, int K, uint64_t M, unsi
 int fedagg_equal_count_f64(const double* const* d_copies, int K, uint64_t M, unsigned long long* d_mismatches,
                            void* stream) {
   return equal_launch<double>(d_copies, K, M, d_mismatches, (hipStream_t)stream);
-}
-
-int fedagg_flat_gather_f32(const float* const* d_layers, const uint64_t* numel, int L, float* d_flat,
-                           void* stream) {
-  return flat_seg_launch<0>(reinterpret_cast<const void* const*>(d_layers), nullptr, 1, nullptr, numel, L, d_flat,
-                            FEDAGG_F32, (hipStream_t)stream);
-}
-int fedagg_flat_scatter_f32(float* const* d_layers, const uint64_t* numel, int L, const float* d_flat, void* stream) {
-  return flat_seg_launch<1>(reinterpret_cast<const void* const*>(d_layers), nullptr, 1, nullptr, numel, L,
-                            const_cast<float*>(d_flat), FEDAGG_F32, (hipStream_t)stream);
-}
-int fedagg_flat_wsum_f32(const float* const* d_layers, int nlists, const double* coeffs, const uint64_t* numel, int L,
-                         float* d_flat, void* stream) {
-  return flat_seg_launch<2>(reinterpret_cast<const void* const*>(d_layers), nullptr, nlists, coeffs, numel, L, d_flat,
-                            FEDAGG_F32, (hipStream_t)stream);
-}
-int fedagg_flat_increment_f32(float* const* d_layers, const uint64_t* numel, int L, const float* d_flat,
-                              double multiplier, void* stream) {
-  return flat_seg_launch<3>(reinterpret_cast<const void* const*>(d_layers), nullptr, 1, &multiplier, numel, L,
-                            const_cast<float*>(d_flat), FEDAGG_F32, (hipStream_t)stream);
-}
-int fedagg_flat_gather(const void* const* d_layers, int kind, const uint64_t* numel, int L, void* d_flat,
-                       void* stream) {
-  if (is_16bit_kind(kind))
-    return flat_seg16_launch<0>(d_layers, kind, 1, nullptr, numel, L, d_flat, kind, (hipStream_t)stream);
-  return flat_seg_launch<0>(d_layers, &kind, 1, nullptr, numel, L, d_flat, kind, (hipStream_t)stream);
-}
-int fedagg_flat_wsum(const void* const* d_layers, const int* kinds, int nlists, const double* coeffs,
-                     const uint64_t* numel, int L, void* d_flat, int flat_kind, void* stream) {
-  if (kinds && nlists >= 1 && nlists <= FEDAGG_FLAT_MAX_LISTS) {
-    bool any16 = is_16bit_kind(flat_kind);
-    for (int j = 0; j < nlists; ++j) any16 = any16 || is_16bit_kind(kinds[j]);
-    if (any16) {  // every list and the result of ONE 16-bit kind; torch's promotion is not done here
-      for (int j = 0; j < nlists; ++j)
-        if (kinds[j] != flat_kind)
-          return fail(FEDAGG_EINVAL, "flat wsum: 16-bit lists take lists and a result of one kind (list %lld)", j);
-      return flat_seg16_launch<2>(d_layers, flat_kind, nlists, coeffs, numel, L, d_flat, flat_kind,
-                                  (hipStream_t)stream);
-    }
-  }
-  return flat_seg_launch<2>(d_layers, kinds, nlists, coeffs, numel, L, d_flat, flat_kind, (hipStream_t)stream);
-}
-int fedagg_flat_increment_kind(void* const* d_layers, int layer_kind, const uint64_t* numel, int L,
-                               const void* d_flat, int flat_kind, double multiplier, void* stream) {
-  const bool ok = (layer_kind == FEDAGG_F16 && flat_kind == FEDAGG_F16) ||
-                  (layer_kind == FEDAGG_BF16 && (flat_kind == FEDAGG_BF16 || flat_kind == FEDAGG_F32));
-  if (!ok)
-    return fail(FEDAGG_EINVAL, "flat increment: unsupported (layer, flat) kinds (flat kind %lld)", flat_kind);
-  return flat_seg16_launch<3>(reinterpret_cast<const void* const*>(d_layers), layer_kind, 1, &multiplier, numel, L,
-                              const_cast<void*>(d_flat), flat_kind, (hipStream_t)stream);
-}
-int fedagg_flat_increment(float* const* d_layers, const uint64_t* numel, int L, const void* d_flat, int flat_kind,
-                          double multiplier, void* stream) {
-  return flat_seg_launch<3>(reinterpret_cast<const void* const*>(d_layers), nullptr, 1, &multiplier, numel, L,
-                            const_cast<void*>(d_flat), flat_kind, (hipStream_t)stream);
 }
 
 static bool is_float_kind(int k) { return k == FEDAGG_F16 || k == FEDAGG_F32 || k == FEDAGG_F64; }

@@ -35,11 +35,7 @@
 #include <thread>
 #include <vector>
 
-#include "fedagg.h"
-
-namespace fedagg_internal {
-void set_error(const char* msg);
-}
+#include "fedagg_internal.h"
 
 namespace {
 

@@ -31,14 +31,8 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 
-#include "fedagg.h"
+#include "fedagg_internal.h"
 #include "host_pool.h"
-
-// defined in fedagg.hip
-extern "C" const char* fedagg_last_error(void);
-namespace fedagg_internal {
-void set_error(const char* msg);
-}
 
 using fedagg_host::Pool;
 using fedagg_host::Ring;

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""Register / LDS / occupancy of every kernel instantiation in fedagg.hip, from the compiler's
+"""Register / LDS / occupancy of every kernel instantiation in one source of csrc/ (--source,
+default fedagg.hip; the client flat ops are in flat_ops.hip), from the compiler's
 code-object metadata (hipcc -Rpass-analysis=kernel-resource-usage; gfx950).  Prints one line per
 kernel: template arguments, VGPRs, AGPRs, scratch bytes per lane, LDS bytes, waves per SIMD.
-Usage: tools/kernel_resources.py [--filter scaffold_kernel] > profiles/<tag>_kernel_resources.txt"""
+Usage: tools/kernel_resources.py [--source flat_ops.hip] [--filter scaffold_kernel] > profiles/<tag>_kernel_resources.txt"""
 
 import argparse
 import re
@@ -17,11 +18,12 @@ ROOT = Path(__file__).resolve().parents[1]
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--filter", default="", help="substring of the demangled kernel name")
+    ap.add_argument("--source", default="fedagg.hip", help="file of substrafl_amd/csrc to compile")
     ap.add_argument("--tuning", action="store_true", help="the FEDAGG_TUNING build (every experiment variant)")
     args = ap.parse_args()
     with tempfile.TemporaryDirectory() as d:
         r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                            "-fPIC", "-c", f"-I{ROOT / 'include'}", str(ROOT / "substrafl_amd" / "csrc" / "fedagg.hip"),
+                            "-fPIC", "-c", f"-I{ROOT / 'include'}", str(ROOT / "substrafl_amd" / "csrc" / args.source),
                             "-o", str(Path(d) / "fa.o"), "-Rpass-analysis=kernel-resource-usage"]
                            + (["-DFEDAGG_TUNING=1"] if args.tuning else []),
                            capture_output=True, text=True)
