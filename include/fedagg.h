@@ -145,6 +145,30 @@ int fedagg_scaffold_f64(const double* const* d_delta, const double* const* d_cv,
  * bucket then the control-variate bucket); in_elem_bytes 4 or 8, aligned = every operand 16-B
  * aligned.  For profilers and benchmarks that attribute kernel time; < 0 on bad arguments. */
 int fedagg_scaffold_launches(int K, int in_elem_bytes, uint64_t M, int aligned);
+/* ONE Scaffold bucket per call, rows of any float kind (scaffold16.hip).  The reference multiplies
+ * every array by a float64 weight, so products and sums are fp64 on the exact upcast of the input
+ * whatever its dtype: a 16-bit model's buckets are read as they are (2 B per element and client)
+ * and widened in registers.  row_kind: FEDAGG_F16 / FEDAGG_BF16 / FEDAGG_F32 / FEDAGG_F64, the
+ * element kind of the K rows d_rows[k] (M elements each).
+ *   phase 0, the delta bucket (scaffold.py:293):
+ *     d_out[i] = lr * (+0.0 + sum_seq_k fl64(h_w[k] * (double)x_k[i]));  d_c is not read (may be NULL)
+ *   phase 1, the control-variate bucket (scaffold.py:262-263), c added LAST:
+ *     d_out[i] = (+0.0 + sum_seq_k fl64(h_w[k] * (double)x_k[i])) + (double)c[i]
+ * c_kind: the kind of d_c, any of the four next to 16-bit rows (c is read once per element, in the
+ * epilogue); next to f32 / f64 rows it must equal row_kind.  No contraction, client order kept,
+ * denormals kept.  numel == 1 elements (h_idx, P >= 0 of them): NumPy's pairwise order over the K
+ * fp64 terms (phase 0, then * lr) or the K + 1 terms (phase 1, c last), as fedagg_scaffold_*; d_ws
+ * (fedagg_pairwise_ws_bytes(K, P, 8) bytes) is needed when the patch cannot be fused.  More than
+ * FEDAGG_KCHUNK_SCAFFOLD clients continue the accumulator in d_out.  16-byte loads when every row,
+ * d_c (phase 1) and d_out are 16-B aligned, a scalar walk with the same values otherwise; any M
+ * (M == 0: FEDAGG_OK, nothing touched).  f32 / f64 rows give, byte for byte, the matching output
+ * of fedagg_scaffold_f32 / _f64. */
+int fedagg_scaffold_bucket(const void* const* d_rows, int row_kind, const double* h_w, int K, uint64_t M, int phase,
+                           const void* d_c, int c_kind, double lr, const uint64_t* h_idx, int P, void* d_ws,
+                           double* d_out, void* stream);
+/* Elements one workgroup step of fedagg_scaffold_bucket covers for rows of row_kind (the tile of
+ * the dispatched shape; workgroups grid-stride over the steps).  0 for an unknown kind. */
+uint64_t fedagg_scaffold_bucket_tile(int row_kind);
 
 /* ---------------------------------------------------------------------------
  * Scaffold server-control-variate check, scaffold.py:193-196

@@ -50,6 +50,9 @@ SIGNATURES = {
         c_int,
         [P(c_void), P(c_void), c_void, P(c_dbl), c_int, c_u64, P(c_u64), c_int, c_void, c_dbl, c_void, c_void, c_void],
     ),
+    "fedagg_scaffold_bucket": (c_int, [P(c_void), c_int, P(c_dbl), c_int, c_u64, c_int, c_void, c_int, c_dbl, P(c_u64),
+                                       c_int, c_void, c_void, c_void]),
+    "fedagg_scaffold_bucket_tile": (c_u64, [c_int]),
     "fedagg_equal_count_f32": (c_int, [P(c_void), c_int, c_u64, c_void, c_void]),
     "fedagg_equal_count_f64": (c_int, [P(c_void), c_int, c_u64, c_void, c_void]),
     "fedagg_read_probe_f32": (c_int, [c_void, c_u64, c_void, c_int, c_void]),

@@ -321,10 +321,22 @@ def set_parameters(model: torch.nn.Module, parameters: List[torch.Tensor], with_
 def zeros_like_parameters(model: torch.nn.Module, with_batch_norm_parameters: bool, device: torch.device):
     with torch.no_grad():
         params = list(model_parameters(model, with_batch_norm_parameters=with_batch_norm_parameters)())
-        if params and torch.device(device).type == "cuda" and all(p.dtype == torch.float32 for p in params):
-            flat = torch.zeros(sum(p.numel() for p in params), dtype=torch.float32, device=device)
+        # one flat bucket for a single-dtype model of a kind the flat ops know (fp16 and bf16 models
+        # too: Scaffold's round-1 control variates then export as one 2-byte bucket)
+        if params and torch.device(device).type == "cuda" and params[0].dtype in _KIND and all(
+                p.dtype == params[0].dtype for p in params):
+            flat = torch.zeros(sum(p.numel() for p in params), dtype=params[0].dtype, device=device)
             return _views(flat, params)
         return [torch.zeros_like(p).to(device) for p in params]
+
+
+def _host_array(t: torch.Tensor) -> np.ndarray:
+    """``t.cpu().detach().numpy()``; a bf16 tensor comes home as ``wire.BF16`` (its bit patterns),
+    any other dtype NumPy lacks raises as the reference's ``.numpy()`` does."""
+    t = t.cpu().detach()
+    if t.dtype == torch.bfloat16:
+        return t.contiguous().view(torch.int16).numpy().view(BF16)
+    return t.numpy()
 
 
 def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = "export") -> List[np.ndarray]:
@@ -338,7 +350,7 @@ def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = 
     first re-faults a fresh buffer for all but one of them."""
     flat = flat_bucket(list(tensors))
     if flat is None or not flat.is_cuda:
-        return [t.cpu().detach().numpy() for t in tensors]
+        return [_host_array(t) for t in tensors]
     from .. import handoff, runtime
 
     # one D2H through the native session's pinned ring (chunked, copied out by its worker pool)

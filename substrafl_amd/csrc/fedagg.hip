@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "fedagg_internal.h"
+#include "pairwise_sum.h"
 
 // FEDAGG_TUNING=1 (`__graft_entry__.build(tuning=True)`, tools/): every launch variant the
 // experiment knobs of fedagg_tune select is instantiated -- the shapes, load paths, occupancy caps
@@ -47,6 +48,8 @@
 
 using fedagg_internal::check_launch;
 using fedagg_internal::fail;
+using fedagg_internal::pw_leaf;
+using fedagg_internal::pw_sum;
 
 namespace {
 
@@ -290,76 +293,6 @@ __device__ __forceinline__ void load_vec(const typename E::Out* out, uint64_t v,
   for (int s = 0; s < bytes / 16; ++s) dst[s] = src[s];
 #pragma unroll
   for (int j = 0; j < E::L; ++j) acc[j] = E::in_out(o[j]);
-}
-
-// ------------------------------------------------------------------------------------
-// NumPy pairwise summation (loops_utils.h.src pairwise_sum, PW_BLOCKSIZE 128), on a
-// generator get(i) of the n terms.  n <= 128: one leaf.
-// ------------------------------------------------------------------------------------
-template <typename T, typename G>
-__device__ __forceinline__ T pw_leaf(const G& get, int64_t lo, int64_t n) {
-#pragma clang fp contract(off)
-  if (n < 8) {
-    T res = T(-0.0);
-    for (int64_t i = 0; i < n; ++i) res = res + get(lo + i);
-    return res;
-  }
-  T r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = get(lo + j);
-  int64_t i = 8;
-  for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = r[j] + get(lo + i + j);
-  }
-  T res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < n; ++i) res = res + get(lo + i);
-  return res;
-}
-
-// Iterative form of the recursive split (n > 128: split at n/2 rounded down to a multiple of 8).
-template <typename T, typename G>
-__device__ T pw_sum(const G& get, int64_t n) {
-#pragma clang fp contract(off)
-  if (n <= 128) return pw_leaf<T>(get, 0, n);
-  int64_t lo[64], nn[64];
-  T left[64];
-  int stage[64];
-  int sp = 0;
-  lo[0] = 0;
-  nn[0] = n;
-  stage[0] = 0;
-  T ret = T(0);
-  for (;;) {
-    while (nn[sp] > 128) {  // descend into left halves
-      int64_t n2 = nn[sp] / 2;
-      n2 -= n2 % 8;
-      stage[sp] = 1;
-      lo[sp + 1] = lo[sp];
-      nn[sp + 1] = n2;
-      stage[sp + 1] = 0;
-      ++sp;
-    }
-    ret = pw_leaf<T>(get, lo[sp], nn[sp]);
-    bool done = true;
-    while (sp > 0) {  // ascend: left done -> start right; right done -> combine
-      --sp;
-      if (stage[sp] == 1) {
-        left[sp] = ret;
-        stage[sp] = 2;
-        int64_t n2 = nn[sp] / 2;
-        n2 -= n2 % 8;
-        lo[sp + 1] = lo[sp] + n2;
-        nn[sp + 1] = nn[sp] - n2;
-        stage[sp + 1] = 0;
-        ++sp;
-        done = false;
-        break;
-      }
-      ret = left[sp] + ret;
-    }
-    if (done) return ret;
-  }
 }
 
 // Tile-interleaved client buckets (fedagg_fedavg_tiled_*): the K clients' tiles of TV 16-B
@@ -2402,6 +2335,8 @@ int check_launch(const char* what) {
   return FEDAGG_OK;
 }
 int flat_vec() { return g_flat_vec; }
+int fuse_pairwise() { return g_fuse_pw; }
+unsigned launch_grid(uint64_t work) { return grid_for(work); }
 }  // namespace fedagg_internal
 
 // ======================================================================================

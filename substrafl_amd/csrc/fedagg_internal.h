@@ -16,5 +16,9 @@ int fail(int code, const char* fmt, long long b = 0);
 int check_launch(const char* what);
 // The "flat_vec" knob of fedagg_tune: 16-B accesses in the client flat ops.
 int flat_vec();
+// The "fuse_pairwise" knob: numel == 1 elements patched inside the bucket launch.
+int fuse_pairwise();
+// Workgroups of FA_BLOCK threads for `work` threads, under the "grid_cap" knob.
+unsigned launch_grid(uint64_t work);
 
 }  // namespace fedagg_internal

@@ -2,7 +2,8 @@
 
 Two entry levels:
 
-* Device-resident plans (``FedAvgPlan`` / ``ScaffoldPlan``): client buckets already in HBM as
+* Device-resident plans (``FedAvgPlan`` / ``ScaffoldPlan`` / ``ScaffoldBucketPlan``, one Scaffold
+  bucket of any float kind, 16-bit rows read as they are): client buckets already in HBM as
   one ``[K, ld]`` tensor or K device pointers; ``plan.launch(stream)`` enqueues the bucket kernel
   (with the numel == 1 pairwise patch fused in).  This is what ``bench.py`` times
   (BASELINE.json metric).
@@ -302,6 +303,56 @@ class ScaffoldPlan:
         return 2 * self.K * self.M * s_in + self.M * s_in + 2 * self.M * 8
 
 
+KIND_CODES = {"f16": _native.FEDAGG_F16, "bf16": _native.FEDAGG_BF16, "f32": _native.FEDAGG_F32,
+              "f64": _native.FEDAGG_F64}
+KIND_BYTES = {"f16": 2, "bf16": 2, "f32": 4, "f64": 8}
+
+
+class ScaffoldBucketPlan:
+    """ONE Scaffold bucket over device-resident rows of any float kind (``fedagg_scaffold_bucket``):
+    ``phase`` 0 the delta rows (``lr * sum``), 1 the control-variate rows (``sum + c``, ``c`` of
+    kind ``c_kind``); fp64 out.  16-bit rows are read as they are and widened in registers."""
+
+    def __init__(self, row_kind: str, rows, phase: int, c, c_kind: Optional[str], weights: np.ndarray, M: int,
+                 lr: float, out, pairwise_idx=None, ws=None):
+        if row_kind not in KIND_CODES or (phase == 1 and c_kind not in KIND_CODES):
+            raise ValueError("ScaffoldBucketPlan: kinds are f16, bf16, f32 or f64")
+        self.lib = _native.load()
+        self.row_kind, self.c_kind, self.phase = row_kind, (c_kind if phase == 1 else None), int(phase)
+        rp = _row_pointers(rows)
+        self.K = len(rp)
+        if self.K == 0 or len(weights) != self.K:
+            raise ValueError("ScaffoldBucketPlan: K mismatch")
+        self.M = int(M)
+        self.lr = float(lr)
+        self._keep = [rows, c, out, ws]
+        self._rp = _native.ptr_array(rp)
+        self._c = _ptr(c) if phase == 1 else 0
+        self._w = (ctypes.c_double * self.K)(*[float(v) for v in np.asarray(weights, np.float64)])
+        self._out = _ptr(out)
+        idx = np.asarray(pairwise_idx if pairwise_idx is not None else [], dtype=np.uint64)
+        self.P = int(idx.size)
+        self._idx = (ctypes.c_uint64 * max(1, self.P))(*[int(v) for v in idx])
+        self._ws = 0
+        if self.P > _native.FEDAGG_FUSED_PAIRWISE or (self.P and self.K > _native.FEDAGG_KCHUNK_SCAFFOLD):
+            if ws is None:
+                torch = _torch()
+                ws = torch.empty(self.lib.fedagg_pairwise_ws_bytes(self.K, self.P, 8), dtype=torch.uint8,
+                                 device=out.device)
+                self._keep.append(ws)
+            self._ws = _ptr(ws)
+
+    def launch(self, stream=None) -> None:
+        rc = self.lib.fedagg_scaffold_bucket(self._rp, KIND_CODES[self.row_kind], self._w, self.K, self.M, self.phase,
+                                             self._c, KIND_CODES[self.c_kind or "f64"], self.lr, self._idx, self.P,
+                                             self._ws, self._out, _stream_handle(stream))
+        _native.check(rc, "scaffold_bucket")
+
+    def bytes_alg(self) -> int:
+        c_bytes = KIND_BYTES[self.c_kind] * self.M if self.phase == 1 else 0
+        return self.K * self.M * KIND_BYTES[self.row_kind] + c_bytes + self.M * 8
+
+
 def equal_count(kind: str, copies, M: int, counter, stream=None) -> None:
     """Enqueue the server-control-variate equality check (adds mismatches to ``counter``)."""
     lib = _native.load()
@@ -350,6 +401,39 @@ def direct_rows(rows: List[List[np.ndarray]], dt: np.dtype, M: int) -> Optional[
     if all(f is not None and f.size == M for f in flats):
         return [[f] for f in flats]
     return [[np.ascontiguousarray(a) for a in row] for row in rows]
+
+
+def bucket_dtype16(rows) -> Optional[np.dtype]:
+    """``float16`` or ``wire.BF16`` when every array of every client in ``rows`` has that one
+    dtype (a 16-bit Scaffold bucket, staged raw), else None."""
+    dts = {np.asarray(a).dtype for row in rows for a in row}
+    if len(dts) == 1:
+        (dt,) = dts
+        if dt == np.float16 or dt == BF16:
+            return dt
+    return None
+
+
+def c_mismatches16(c_rows) -> Tuple[int, str]:
+    """Scaffold's server-control-variate check (scaffold.py:193-196) on the host for fp16 or
+    ``wire.BF16`` copies: ``(mismatching elements of rows[1:] against rows[0], path)``.  Copies
+    byte-identical to row 0 are equal (``"host-bytes"``); only otherwise are values compared
+    (``"host-values"``): fp16 natively, bf16 through its exact fp32 upcast, with +0 == -0 and
+    NaN == NaN as ``assert_array_equal`` has them."""
+    from .wire import bf16_to_float32
+
+    mism, path = 0, "host-bytes"
+    for row in c_rows[1:]:
+        for a, b in zip(c_rows[0], row):
+            if a is b:
+                continue
+            a, b = np.ascontiguousarray(a).reshape(-1), np.ascontiguousarray(b).reshape(-1)
+            if np.array_equal(a.view(np.uint16), b.view(np.uint16)):
+                continue
+            path = "host-values"
+            va, vb = (bf16_to_float32(a), bf16_to_float32(b)) if a.dtype == BF16 else (a, b)
+            mism += int(np.count_nonzero(~((va == vb) | (np.isnan(va) & np.isnan(vb)))))
+    return mism, path
 
 
 def serialized(method):
@@ -525,10 +609,18 @@ class AggregationEngine:
             row = list(getattr(state, field, None) or [])
             if not row or not all(isinstance(a, np.ndarray) for a in row):
                 return None
-            if any(a.dtype != row[0].dtype for a in row) or row[0].dtype.kind not in "biuf":
+            if any(a.dtype != row[0].dtype for a in row) or not (
+                    row[0].dtype.kind in "biuf" or (strategy == "scaffold" and row[0].dtype == BF16)):
                 return None  # per-layer dtype groups are staged by the aggregation call
             rows.append(row)
-        if strategy == "scaffold":  # scaffold engine: fp32 buckets only when every list is fp32
+        buckets16 = strategy == "scaffold" and any(bucket_dtype16([r]) is not None for r in rows)
+        if buckets16:  # kinds per bucket, as scaffold_per_bucket stages them: 16-bit rows raw
+            c_row = []  # (c is staged and checked by the aggregation call)
+            c32 = all(isinstance(a, np.ndarray) and a.dtype == np.float32
+                      for a in list(getattr(state, "server_control_variate", None) or []))
+            targets = [bucket_dtype16([r]) or np.dtype(np.float32 if r[0].dtype == np.float32 and (i == 0 or c32)
+                                                       else np.float64) for i, r in enumerate(rows)]
+        elif strategy == "scaffold":  # scaffold engine: fp32 buckets only when every list is fp32
             c_row = list(getattr(state, "server_control_variate", None) or [])
             all32 = all(r[0].dtype == np.float32 for r in rows) and all(
                 isinstance(a, np.ndarray) and a.dtype == np.float32 for a in c_row)
@@ -1117,6 +1209,120 @@ class AggregationEngine:
             s.copy_d2d(hc, cout, lay_c.M * 8)
             s.sync()
             handoff.record_slot(out_c, s, self._B_HANDOFF_C, hc, stable=True)
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        avg = [a for _, a in lay_d.unpack(out_d, wire)]
+        new_c = [a for _, a in lay_c.unpack(out_c, wire)]
+        tm["total_s"] = time.perf_counter() - t_start
+        return int(mism[0]) + host_mism, new_c, avg
+
+    @staticmethod
+    def _float_rows(rows) -> None:
+        """Refuse ``wire.BF16`` (mixed into another bucket) and dtypes without an exact fp64 cast."""
+        reject_bf16(rows, "Scaffold engine")
+        for client in rows:
+            for a in client:
+                if a.dtype.kind not in "biuf" or a.dtype == np.longdouble:
+                    raise NotImplementedError(f"Scaffold engine: unsupported dtype {a.dtype}")
+
+    def scaffold_per_bucket(self, parameters_updates, control_variate_updates, server_control_variates,
+                            n_samples: Sequence[int], aggregation_lr, wire: bool = False):
+        """:meth:`scaffold` with kinds per bucket: what the strategies call.  When the delta or the
+        control-variate bucket is 16-bit (every array of every client fp16, or every one
+        ``wire.BF16``) each bucket is staged in its own kind and reduced by one
+        ``fedagg_scaffold_bucket`` launch; otherwise this is :meth:`scaffold`, which itself keeps
+        one kind per call (fp16 promoted to fp64 in HBM, ``wire.BF16`` refused).  Same return."""
+        if (not parameters_updates or not parameters_updates[0] or (
+                bucket_dtype16(parameters_updates) is None and bucket_dtype16(control_variate_updates) is None)):
+            return self.scaffold(parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                                 aggregation_lr, wire)
+        return self._scaffold_buckets(parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                                      aggregation_lr, wire)
+
+    @serialized
+    def _scaffold_buckets(self, pus, cvs, scv, n_samples, aggregation_lr, wire: bool):
+        """At least one bucket is 16-bit: kinds per bucket, one launch each.  A 16-bit
+        bucket is staged raw (2-byte rows, no device cast) and widened in the kernel's registers;
+        another bucket is f32 when all of its arrays are (for the control-variate bucket, c too),
+        else f64 through the exact cast.  c keeps its own kind next to a 16-bit control-variate
+        bucket.  The reference's products and sums are fp64 on the exact upcasts whatever the
+        dtype (float64 weights are strong scalars), so the results are those of the promoted
+        route, bit for bit."""
+        t_start = time.perf_counter()
+        pus, cvs, scv = (native_byte_order(x) for x in (pus, cvs, scv))
+        s = self.session()
+        self.last_timing = tm = {}
+        K, L = len(pus), len(pus[0])
+        f32, f64 = np.dtype(np.float32), np.dtype(np.float64)
+        c_dts = {a.dtype for row in scv for a in row}
+        c_dt = next(iter(c_dts)) if len(c_dts) == 1 else None
+        if c_dt is not None and not (c_dt == BF16 or c_dt in (np.float16, f32, f64)):
+            c_dt = None
+
+        def bucket_dtype(rows, with_c: bool) -> np.dtype:
+            dt = bucket_dtype16(rows)
+            if dt is not None:
+                return dt
+            self._float_rows(rows)
+            all32 = all(a.dtype == f32 for row in rows for a in row) and (not with_c or c_dt == f32)
+            return f32 if all32 else f64
+
+        dt_d, dt_c = bucket_dtype(pus, False), bucket_dtype(cvs, True)
+        # c: raw in its own kind next to a 16-bit control-variate bucket, else cast to the bucket's
+        dt_s = (c_dt if c_dt is not None else f64) if dt_c.itemsize == 2 else dt_c
+        if dt_s != c_dt:
+            self._float_rows(scv)
+        lid = list(range(L))
+        lay_d = BucketLayout(lid, [a.shape for a in pus[0]], dt_d)
+        lay_c = BucketLayout(lid, [a.shape for a in cvs[0]], dt_c)
+        lay_s = BucketLayout(lid, [a.shape for a in scv[0]], dt_s)
+        tm["bucket_kinds"] = (kind_of(dt_d), kind_of(dt_c), kind_of(dt_s))
+        w = scaffold_weights(n_samples)
+        lr = float(aggregation_lr)
+        t0 = time.perf_counter()
+        same_c = all(len(row) == len(scv[0]) and all(a is b for a, b in zip(row, scv[0])) for row in scv[1:])
+        host_c = not same_c and c_dt is not None and (c_dt.itemsize == 2 or self.c_check == "host")
+        Kc = 1 if (same_c or host_c) else K
+        d_d = s.buffer(self._B_BUCKET, K * lay_d.ld * dt_d.itemsize)
+        d_cv = s.buffer(self._B_CV, K * lay_c.ld * dt_c.itemsize)
+        d_cc = s.buffer(self._B_C, Kc * lay_s.ld * dt_s.itemsize)
+        pre = 0
+        self._handoff_keep = None
+        for rows, lay, d, slot in ((pus, lay_d, d_d, self._B_BUCKET), (cvs, lay_c, d_cv, self._B_CV)):
+            rows = [list(r) for r in rows]
+            if self._take_prestaged(slot, d, lay.ld * lay.dtype.itemsize, rows):
+                pre += 1
+            else:
+                self._stage_rows(s, rows, lay, d)
+        c_rows = [list(r) for r in scv]
+        host_mism, c_path = 0, "identity" if same_c else "device"
+        if host_c and c_dt.itemsize == 2:
+            host_mism, c_path = c_mismatches16(c_rows)
+        elif host_c:
+            host_mism, c_path = s.check(c_rows, c_dt), "host"
+        self._stage_rows(s, c_rows[:Kc], lay_s, d_cc)
+        self._prestaged = {}
+        tm["prestaged"] = pre == 2
+        tm["c_check"] = c_path
+        tm["stage_s"] = time.perf_counter() - t0
+        t1 = time.perf_counter()
+        cnt = s.buffer(self._B_CNT, 8)
+        s.memset(cnt, 0, 8)
+        if Kc == K and K > 1:
+            equal_count(kind_of(dt_s), [d_cc + k * lay_s.ld * dt_s.itemsize for k in range(K)], lay_s.M, cnt, s.stream)
+        dout = s.buffer(self._B_OUT, lay_d.ld * 8)
+        cout = s.buffer(self._B_COUT, lay_c.ld * 8)
+        ws = s.buffer(self._B_WS, _native.load().fedagg_pairwise_ws_bytes(
+            K, max(1, lay_d.pairwise_idx.size, lay_c.pairwise_idx.size), 8))
+        ScaffoldBucketPlan(kind_of(dt_d), [d_d + k * lay_d.ld * dt_d.itemsize for k in range(K)], 0, None, None, w,
+                           lay_d.M, lr, dout, lay_d.pairwise_idx, ws).launch(s.stream)
+        ScaffoldBucketPlan(kind_of(dt_c), [d_cv + k * lay_c.ld * dt_c.itemsize for k in range(K)], 1, d_cc,
+                           kind_of(dt_s), w, lay_c.M, lr, cout, lay_c.pairwise_idx, ws).launch(s.stream)
+        out_d = runtime.reusable_host_array(lay_d.M, np.float64, "scaffold-delta")
+        out_c = runtime.reusable_host_array(lay_c.M, np.float64, "scaffold-c")
+        mism = np.zeros(1, np.int64)
+        s.fetch(cnt, mism)
+        s.fetch(dout, out_d)
+        s.fetch(cout, out_c)
         tm["kernel_fetch_s"] = time.perf_counter() - t1
         avg = [a for _, a in lay_d.unpack(out_d, wire)]
         new_c = [a for _, a in lay_c.unpack(out_c, wire)]

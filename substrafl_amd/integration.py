@@ -174,7 +174,9 @@ def scaffold_average(strategy, shared_states, aggregation_lr, device: Optional[D
     c0 = list(shared_states[0].server_control_variate)
     check_same_shapes([*cvs, c0])  # np.sum([w*cv_k ..., c]) (scaffold.py:263)
     check_same_shapes(pus)  # np.sum([w*Δ_k ...]) (scaffold.py:293)
-    mismatches, new_c, avg = engine_for(device).scaffold(
+    engine = engine_for(device)
+    # kinds per bucket where the engine has them (16-bit buckets on one GPU), else one kind per call
+    mismatches, new_c, avg = getattr(engine, "scaffold_per_bucket", engine.scaffold)(
         pus, cvs, _MirrorScaffold._server_control_variates(shared_states), [s.n_samples for s in shared_states],
         aggregation_lr, wire=wire)
     assert mismatches == 0, "all server_control_variate in the shared_states are not equal"
