@@ -16,6 +16,9 @@
  *     capturable into a hipGraph.
  *   - `stream` is a hipStream_t (NULL = the legacy default stream).  Every call is
  *     asynchronous on that stream.
+ *   - Not covered by these two promises: fedagg_lockstep_execute and fedagg_push_execute
+ *     (several streams, RCCL and other processes; see their own text) and
+ *     fedagg_copy_async (FEDAGG_TUNING build only).
  *   - Return value: 0 on success, a negative FEDAGG_E* code otherwise;
  *     fedagg_last_error() gives the message of the calling thread's last failure.
  *   - Arithmetic is bit-exact with the reference NumPy path (no FMA contraction,
