@@ -11,7 +11,11 @@ imports ``/root/reference`` in the build container and calls
 ``FedAvg.avg_shared_states`` / ``Scaffold.avg_shared_states`` with
 ``_skip=True``) and against the reference's own unit-test known answers
 (``tests/strategies/test_fed_avg.py:17-65``,
-``tests/strategies/test_scaffold.py:22-198``).
+``tests/strategies/test_scaffold.py:22-198``).  The non-fp32 paths -- fp16 / fp64 /
+integer / mixed-dtype FedAvg, non-finite values, the 16-bit and fp64 Scaffold
+kinds up to K = 257, the reference's fp16 simulations -- are pinned the same way
+by ``tests/golden/gen_golden_dtypes.py`` and ``gen_plumbing_half.py``
+(``tests/test_golden_dtypes.py``).
 """
 
 from .aggregation import (  # noqa: F401

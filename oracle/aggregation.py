@@ -106,11 +106,13 @@ def fedavg_reference_structure(parameters_updates: List[List[np.ndarray]], n_sam
 
 
 def fedavg_explicit(parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int]):
-    """Explicit-order restatement for same-dtype fp32/fp64 layers.
+    """Explicit-order restatement for same-dtype fp16/fp32/fp64 layers.
 
     ``p_k = fl(x_k * fl(w_k))``; numel >= 2: ``acc = +0.0; acc = fl(acc + p_k)`` in list order
     (NumPy seeds the reduction with the +0.0 identity: an all ``-0.0`` column sums to ``+0.0``);
-    numel == 1: ``+0.0 + pairwise(p_0..p_{K-1})``.
+    numel == 1: ``+0.0 + pairwise(p_0..p_{K-1})``.  fp16: products and the chain round to fp16
+    at every step, but NumPy's half pairwise sum adds the upcast products in fp32 and rounds once,
+    ``fl16(fl32(+0.0) + pairwise_fp32(p))`` (pinned by tests/golden/golden_dtypes.npz).
     """
     n_all = sum(int(n) for n in n_samples)
     out = []
@@ -119,8 +121,11 @@ def fedavg_explicit(parameters_updates: List[List[np.ndarray]], n_samples: Seque
         w = np.array([int(n) / n_all for n in n_samples], dtype=np.float64).astype(dtype)
         prods = [np.multiply(pu[idx], w[k], dtype=dtype) for k, pu in enumerate(parameters_updates)]
         if prods[0].size == 1:
-            vals = np.array([p.reshape(-1)[0] for p in prods], dtype=dtype)
-            out.append(np.full(prods[0].shape, dtype.type(0.0) + numpy_pairwise_sum(vals), dtype=dtype))
+            acc_dtype = np.dtype(np.float32) if dtype == np.float16 else dtype
+            vals = np.array([p.reshape(-1)[0] for p in prods], dtype=acc_dtype)
+            with np.errstate(over="ignore", invalid="ignore"):
+                total = dtype.type(acc_dtype.type(0.0) + numpy_pairwise_sum(vals))
+            out.append(np.full(prods[0].shape, total, dtype=dtype))
         else:
             acc = np.zeros(prods[0].shape, dtype=dtype)
             for p in prods:

@@ -47,7 +47,13 @@ def linear_data(n_col=3, n_samples=11, weights_seed=42, noise_seed=12):
     return np.c_[random_content, target]
 
 
-def main():
+def harness(dtype=None):
+    """The reference's simulation with an in-memory data layer and recording strategies: a namespace
+    with ``run`` (one simulation; its aggregations go into ``arrays`` / ``meta``), ``arrays``,
+    ``meta``, ``torch``, the recording strategies and the algo bases.  ``dtype``: the torch dtype the
+    dataset hands the model (default float32, as the reference's own test dataset); ``cfg["dtype"]``
+    of the namespace changes it between runs."""
+    cfg = {"dtype": dtype}
     if not REF.exists():
         raise SystemExit("gen_plumbing.py needs /root/reference (build container only)")
     _install_stubs()
@@ -100,10 +106,10 @@ def main():
             self.is_inference = is_inference
 
         def __getitem__(self, index):
-            x = torch.from_numpy(self.x[index]).float()
+            x = torch.from_numpy(self.x[index]).to(cfg["dtype"] or torch.float32)
             if not self.is_inference:
                 y = torch.as_tensor(self.y[index])
-                y = y.float() if y.dtype.is_floating_point else y.long()
+                y = y.to(cfg["dtype"] or torch.float32) if y.dtype.is_floating_point else y.long()
                 return x, y
             return x
 
@@ -164,11 +170,25 @@ def main():
             calls.append({"key": key, "K": len(states), "layers": L, "kind": kind, "aggregation_lr": alr,
                           "shapes": [list(a.shape) for a in states[0].parameters_update],
                           "dtypes": [str(a.dtype) for a in states[0].parameters_update]})
+            if cfg["dtype"] is not None:  # every kind of the call: inputs per bucket, outputs
+                kinds = lambda rows: sorted({str(a.dtype) for r in rows for a in r})  # noqa: E731
+                calls[-1]["kinds"] = {"pu": kinds(s.parameters_update for s in states),
+                                      "out_avg": kinds([out.avg_parameters_update])}
+                if kind == "scaffold":
+                    calls[-1]["kinds"].update(cv=kinds(s.control_variate_update for s in states),
+                                              c=kinds(s.server_control_variate for s in states),
+                                              out_c=kinds([out.server_control_variate]))
         meta["configs"][name] = {"calls": calls, "final_performance": final, "rounds": rounds}
         print(f"{name}: {len(calls)} aggregations, final performance {final!r}")
         return final
 
-    # --- the reference's own linear known answer (FedAvg, then Scaffold) ---
+    return types.SimpleNamespace(run=run, cfg=cfg, arrays=arrays, meta=meta, torch=torch, RecFedAvg=RecFedAvg,
+                                 RecScaffold=RecScaffold, TorchFedAvgAlgo=TorchFedAvgAlgo,
+                                 TorchScaffoldAlgo=TorchScaffoldAlgo, mae_score=mae_score, acc_score=acc_score)
+
+
+def linear_setup(torch):
+    """The reference's 2-org linear known-answer setup: (train sets, test set, split, Perceptron)."""
     train = [linear_data(n_col=3, n_samples=1024, weights_seed=42, noise_seed=i) for i in range(2)]
     test = linear_data(n_col=3, n_samples=64, weights_seed=42, noise_seed=42)
     split = lambda d: (d[:, :-1], d[:, -1:])  # noqa: E731  (the NumpyOpener, assets_factory.py:23-31)
@@ -181,6 +201,34 @@ def main():
         def forward(self, x):
             return self.linear1(x)
 
+    return train, test, split, Perceptron
+
+
+def small_cnn(torch):
+    """Conv + BatchNorm running statistics + linear, for 1x28x28 inputs."""
+
+    class SmallCNN(torch.nn.Module):
+        def __init__(self):
+            super().__init__()
+            self.conv = torch.nn.Conv2d(1, 8, 3)
+            self.bn = torch.nn.BatchNorm2d(8)
+            self.fc = torch.nn.Linear(8 * 13 * 13, 10)
+
+        def forward(self, x):
+            x = torch.nn.functional.max_pool2d(torch.relu(self.bn(self.conv(x))), 2)
+            return self.fc(x.flatten(1))
+
+    return SmallCNN
+
+
+def main():
+    h = harness()
+    run, arrays, meta, torch = h.run, h.arrays, h.meta, h.torch
+    RecFedAvg, RecScaffold, TorchFedAvgAlgo, TorchScaffoldAlgo = (h.RecFedAvg, h.RecScaffold, h.TorchFedAvgAlgo,
+                                                                 h.TorchScaffoldAlgo)
+    mae_score, acc_score = h.mae_score, h.acc_score
+    # --- the reference's own linear known answer (FedAvg, then Scaffold) ---
+    train, test, split, Perceptron = linear_setup(torch)
     torch.manual_seed(42)
     perf = run("linear_fedavg", RecFedAvg, TorchFedAvgAlgo, Perceptron(), torch.nn.MSELoss(),
                [split(d) for d in train], split(test), mae_score, rounds=3)
@@ -194,17 +242,7 @@ def main():
     g = np.random.default_rng(2024)
     mk = lambda n: (g.standard_normal((n, 1, 28, 28)).astype(np.float32), g.integers(0, 10, n))  # noqa: E731
 
-    class SmallCNN(torch.nn.Module):
-        def __init__(self):
-            super().__init__()
-            self.conv = torch.nn.Conv2d(1, 8, 3)
-            self.bn = torch.nn.BatchNorm2d(8)
-            self.fc = torch.nn.Linear(8 * 13 * 13, 10)
-
-        def forward(self, x):
-            x = torch.nn.functional.max_pool2d(torch.relu(self.bn(self.conv(x))), 2)
-            return self.fc(x.flatten(1))
-
+    SmallCNN = small_cnn(torch)
     torch.manual_seed(7)
     run("mnist_fedavg", RecFedAvg, TorchFedAvgAlgo, SmallCNN(), torch.nn.CrossEntropyLoss(),
         [mk(256), mk(192)], mk(64), acc_score, rounds=2, lr=0.05, updates=8, batch=32,
