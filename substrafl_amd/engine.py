@@ -164,14 +164,15 @@ class FedAvgPlan:
         idx = np.asarray(pairwise_idx if pairwise_idx is not None else [], dtype=np.uint64)
         self.P = int(idx.size)
         self._idx = (ctypes.c_uint64 * max(1, self.P))(*[int(v) for v in idx])
-        self._ws = 0
-        if self.P > _native.FEDAGG_FUSED_PAIRWISE or (self.P and self.K > _native.FEDAGG_KCHUNK):
-            if ws is None:  # the numel==1 patch cannot be fused into the bucket launch
-                torch = _torch()
-                nbytes = self.lib.fedagg_pairwise_ws_bytes(self.K, self.P, 8)
-                ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
-                self._keep = (clients, out, ws)
-            self._ws = _ptr(ws)
+        # a workspace the caller gives is always passed on: with the fuse_pairwise knob off the
+        # library takes the separate gather / tree path for any P > 0 and needs it
+        if ws is None and (self.P > _native.FEDAGG_FUSED_PAIRWISE or (self.P and self.K > _native.FEDAGG_KCHUNK)):
+            # the numel==1 patch cannot be fused into the bucket launch
+            torch = _torch()
+            nbytes = self.lib.fedagg_pairwise_ws_bytes(self.K, self.P, 8)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=out.device)
+            self._keep = (clients, out, ws)
+        self._ws = _ptr(ws) if ws is not None else 0
         self._main = getattr(self.lib, f"fedagg_fedavg_{kind}")
 
     def launch(self, stream=None) -> None:

@@ -7,6 +7,15 @@
   traced);
 * ``unreachable``: no call of the product build launches it; the reason quotes the dispatch.
 
+Every ``fedavg_kernel`` has rows, the three of the tile-interleaved layout (last template argument
+8192, 2048, 4096) included.  Over ``tests/test_tiled_layout.py``, which keeps its cases (K > 128,
+P = 17, the random sweep), their rows add: a grid-capped launch in which workgroups walk a second
+tile; a tiled buffer built from the layout of ``include/fedagg.h`` instead of the engine's helpers,
+with NaN in all padding; a guard band behind the output; planted +-0 / subnormal / largest-finite
+values and all -0 columns; the r = ``(VPT - 1) * threads + 100`` remainder; a one-launch
+``fedagg_fedavg_chain_tiled_*`` continuation of a known accumulator; the separate gather / tree
+path with an index behind tile 0; and buckets of 1, L - 1, L, L + 1 and one tile -1 / 0 / +1 elements.
+
 ``tests/test_product_kernel_manifest.py`` keeps this file, the committed kernel list, the built
 library and the kernel trace of the rows (profiles/product_dispatch_trace.txt) in step."""
 
@@ -37,8 +46,18 @@ MANIFEST = {
         "fa-bf16-16x2-nt-K33-r0", "fa-bf16-16x2-nt-K33-r37-pw", "fa-bf16-16x2-nt-K33-rbig",
         "fa-bf16-16x2-nt-K33-cap500", "fa-bf16-16x2-nt-K33-r37-chain",
     ]),
-    "fedavg_kernel<BF16, 128, true, 1, 16, 2, false, true, 1, true, 256, 4096>": dict(
-        covered_by="tests/test_tiled_layout.py::test_tiled_fedavg_bit_exact"),
+    "fedavg_kernel<BF16, 128, true, 1, 16, 2, false, true, 1, true, 256, 4096>": dict(rows=[
+        "fa-bf16-tiled4096-nt-K33-r0", "fa-bf16-tiled4096-nt-K33-r37-pw", "fa-bf16-tiled4096-nt-K33-rbig",
+        "fa-bf16-tiled4096-nt-K33-cap3-pw", "fa-bf16-tiled4096-nt-K33-r37-chain", "fa-bf16-tiled4096-nt-K5-r0",
+        "fa-bf16-tiled4096-nt-K5-r37-pw", "fa-bf16-tiled4096-nt-K5-rbig", "fa-bf16-tiled4096-nt-K5-cap3-pw",
+        "fa-bf16-tiled4096-nt-K5-r37-chain", "fa-bf16-tiled4096-nt-K33-r37-unfused",
+        "fa-bf16-tiled4096-nt-K1-small-M1", "fa-bf16-tiled4096-nt-K1-small-Lm1", "fa-bf16-tiled4096-nt-K1-small-L",
+        "fa-bf16-tiled4096-nt-K1-small-Lp1", "fa-bf16-tiled4096-nt-K1-small-TLm1",
+        "fa-bf16-tiled4096-nt-K1-small-TL", "fa-bf16-tiled4096-nt-K1-small-TLp1",
+        "fa-bf16-tiled4096-nt-K5-small-M1", "fa-bf16-tiled4096-nt-K5-small-Lm1", "fa-bf16-tiled4096-nt-K5-small-L",
+        "fa-bf16-tiled4096-nt-K5-small-Lp1", "fa-bf16-tiled4096-nt-K5-small-TLm1",
+        "fa-bf16-tiled4096-nt-K5-small-TL", "fa-bf16-tiled4096-nt-K5-small-TLp1",
+    ]),
     "fedavg_kernel<BF16, 128, true, 1, 2, 8, false, true, 1, false, 256, 0>": dict(rows=[
         "fa-bf16-2x8-nt-K33-r0", "fa-bf16-2x8-nt-K33-r37-pw", "fa-bf16-2x8-nt-K33-rbig", "fa-bf16-2x8-nt-K33-cap3",
         "fa-bf16-2x8-nt-K33-r37-chain", "fa-bf16-2x8-nt-K33-below-short", "fa-bf16-2x8-nt-K32-at-short-M",
@@ -112,8 +131,17 @@ MANIFEST = {
         "fa-f32-16x2-nt-K33-r0", "fa-f32-16x2-nt-K33-r37-pw", "fa-f32-16x2-nt-K33-rbig", "fa-f32-16x2-nt-K33-cap500",
         "fa-f32-16x2-nt-K33-r37-chain",
     ]),
-    "fedavg_kernel<F32, 128, true, 1, 16, 2, false, true, 1, false, 512, 8192>": dict(
-        covered_by="tests/test_tiled_layout.py::test_tiled_fedavg_bit_exact"),
+    "fedavg_kernel<F32, 128, true, 1, 16, 2, false, true, 1, false, 512, 8192>": dict(rows=[
+        "fa-f32-tiled8192-nt-K33-r0", "fa-f32-tiled8192-nt-K33-r37-pw", "fa-f32-tiled8192-nt-K33-rbig",
+        "fa-f32-tiled8192-nt-K33-cap3-pw", "fa-f32-tiled8192-nt-K33-r37-chain", "fa-f32-tiled8192-nt-K5-r0",
+        "fa-f32-tiled8192-nt-K5-r37-pw", "fa-f32-tiled8192-nt-K5-rbig", "fa-f32-tiled8192-nt-K5-cap3-pw",
+        "fa-f32-tiled8192-nt-K5-r37-chain", "fa-f32-tiled8192-nt-K33-r37-unfused",
+        "fa-f32-tiled8192-nt-K1-small-M1", "fa-f32-tiled8192-nt-K1-small-Lm1", "fa-f32-tiled8192-nt-K1-small-L",
+        "fa-f32-tiled8192-nt-K1-small-Lp1", "fa-f32-tiled8192-nt-K1-small-TLm1", "fa-f32-tiled8192-nt-K1-small-TL",
+        "fa-f32-tiled8192-nt-K1-small-TLp1", "fa-f32-tiled8192-nt-K5-small-M1", "fa-f32-tiled8192-nt-K5-small-Lm1",
+        "fa-f32-tiled8192-nt-K5-small-L", "fa-f32-tiled8192-nt-K5-small-Lp1", "fa-f32-tiled8192-nt-K5-small-TLm1",
+        "fa-f32-tiled8192-nt-K5-small-TL", "fa-f32-tiled8192-nt-K5-small-TLp1",
+    ]),
     "fedavg_kernel<F32, 128, true, 1, 2, 8, false, true, 1, false, 256, 0>": dict(rows=[
         "fa-f32-2x8-nt-K33-r0", "fa-f32-2x8-nt-K33-r37-pw", "fa-f32-2x8-nt-K33-rbig", "fa-f32-2x8-nt-K33-cap3",
         "fa-f32-2x8-nt-K33-r37-chain", "fa-f32-2x8-nt-K33-below-short", "fa-f32-2x8-nt-K32-at-short-M",
@@ -146,8 +174,18 @@ MANIFEST = {
         "fa-f32-8x4-sc1-K5-cap3", "fa-f32-8x4-sc1-K5-r37-chain", "fa-f32-8x4-sc1-K33-below-big",
         "fa-f32-8x4-sc1-K31-at-short-M", "fa-f32-8x4-sc1-K8-r37-pw",
     ]),
-    "fedavg_kernel<F32, 128, true, 2, 8, 4, false, true, 1, false, 256, 2048>": dict(
-        covered_by="tests/test_tiled_layout.py::test_tiled_fedavg_bit_exact"),
+    "fedavg_kernel<F32, 128, true, 2, 8, 4, false, true, 1, false, 256, 2048>": dict(rows=[
+        "fa-f32-tiled2048-sc1-K5-r0", "fa-f32-tiled2048-sc1-K5-r37-pw", "fa-f32-tiled2048-sc1-K5-rbig",
+        "fa-f32-tiled2048-sc1-K5-cap3-pw", "fa-f32-tiled2048-sc1-K5-r37-chain", "fa-f32-tiled2048-sc1-K33-r0",
+        "fa-f32-tiled2048-sc1-K33-r37-pw", "fa-f32-tiled2048-sc1-K33-rbig", "fa-f32-tiled2048-sc1-K33-cap3-pw",
+        "fa-f32-tiled2048-sc1-K33-r37-chain", "fa-f32-tiled2048-sc1-K5-r37-unfused",
+        "fa-f32-tiled2048-sc1-K1-small-M1", "fa-f32-tiled2048-sc1-K1-small-Lm1", "fa-f32-tiled2048-sc1-K1-small-L",
+        "fa-f32-tiled2048-sc1-K1-small-Lp1", "fa-f32-tiled2048-sc1-K1-small-TLm1",
+        "fa-f32-tiled2048-sc1-K1-small-TL", "fa-f32-tiled2048-sc1-K1-small-TLp1",
+        "fa-f32-tiled2048-sc1-K5-small-M1", "fa-f32-tiled2048-sc1-K5-small-Lm1", "fa-f32-tiled2048-sc1-K5-small-L",
+        "fa-f32-tiled2048-sc1-K5-small-Lp1", "fa-f32-tiled2048-sc1-K5-small-TLm1",
+        "fa-f32-tiled2048-sc1-K5-small-TL", "fa-f32-tiled2048-sc1-K5-small-TLp1",
+    ]),
     "fedavg_kernel<F32, 128, true, 3, 16, 2, false, true, 1, false, 512, 0>": dict(rows=[
         "fa-f32-16x2-sys-K33-r0-null", "fa-f32-16x2-sys-K33-r37-sep", "fa-f32-16x2-sys-K33-rbig-sep",
         "fa-f32-16x2-sys-K33-cap500-null",
@@ -204,16 +242,18 @@ MANIFEST = {
         covered_by="tests/test_half_client_ops_gpu.py::test_native_increment_same_kind_bit_exact"),
     "flat_typed_kernel<3, 12, true>": dict(
         covered_by="tests/test_half_client_ops_gpu.py::test_native_increment_bf16_by_fp32_promoted_add"),
-    "pairwise_gather_kernel<BF16, 128>": dict(
-        covered_by="tests/test_tiled_layout.py::test_tiled_fedavg_bit_exact"),
+    "pairwise_gather_kernel<BF16, 128>": dict(rows=[
+        "fa-bf16-tiled4096-nt-K33-r37-unfused",
+    ]),
     "pairwise_gather_kernel<F16, 128>": dict(
         covered_by="tests/test_multi_abi_gpu.py::test_multi_entry_bit_exact"),
     "pairwise_gather_kernel<F32, 128>": dict(
         covered_by="tests/test_gpu_parity.py::test_many_numel1_layers_fused_and_separate"),
     "pairwise_gather_kernel<F64, 128>": dict(
         covered_by="tests/test_multi_abi_gpu.py::test_multi_entry_bit_exact"),
-    "pairwise_tree_kernel<BF16>": dict(
-        covered_by="tests/test_tiled_layout.py::test_tiled_fedavg_bit_exact"),
+    "pairwise_tree_kernel<BF16>": dict(rows=[
+        "fa-bf16-tiled4096-nt-K33-r37-unfused",
+    ]),
     "pairwise_tree_kernel<F16>": dict(
         covered_by="tests/test_multi_abi_gpu.py::test_multi_entry_bit_exact"),
     "pairwise_tree_kernel<F32>": dict(

@@ -11,6 +11,16 @@ path in a wave that is not ``wave_full`` and the per-vector fallback side by sid
 client-count threshold; one grid-capped launch per shape (a workgroup walks several tiles); a
 chain / push continuation of an accumulator (``first == 0``).
 
+The three kernels of the tile-interleaved layout (``fedagg_fedavg_tiled_<kind>``,
+``fedagg_fedavg_chain_tiled_<kind>``) get the same family per (tile, client count), at two tiles
+plus the remainder, with a grid cap of 3 over five tiles (two workgroups walk a second tile, so
+``t * pitch`` counts for ``it > 0``), the numel == 1 indices fused and through the separate
+gather / tree path with its tiled index map, and the smallest buckets (M = 1, L - 1, L, L + 1,
+one tile -1 / 0 / +1).  Their buffer is built from the layout ``include/fedagg.h`` publishes, not
+with the engine's layout helpers, and everything in it that is no client's element [0, M) -- the
+pad of the last tile, in every client -- is a quiet NaN: one pad read that reaches an output, or a
+read from the next client's tile at the wrong pitch, shows.
+
 References
   * fp32 / bf16 / fp64 FedAvg below 1M elements: the oracle (``fedavg_reference_structure``) on
     the exact upcast, the ``numel == 1`` indices as one-element layers; seeded continuations:
@@ -138,7 +148,61 @@ def _fedavg_cases():
 FEDAVG_CASES = _fedavg_cases()
 
 
-def _tile_of(c: FaCase) -> int:
+# =============================================================================================
+# Tile-interleaved FedAvg case table (fedagg_fedavg_tiled_<kind>, fedagg_fedavg_chain_tiled_<kind>)
+# =============================================================================================
+# The three tiled kernels: (kind, tile T in 16-B vectors, vectors per thread, threads, store build,
+# client counts).  The entry points take any K with any of their tiles; K <= 128 keeps a case one
+# fedavg_kernel launch.  entry: "main" (engine.TiledFedAvgPlan, takes idx), "chain" (seed = 0:
+# continues d_out).  fuse: the fuse_pairwise knob (0: separate gather / tree with the tiled map).
+TILED_TILES = (("f32", 8192, 16, 512, "nt", (33, 5)),
+               ("f32", 2048, 8, 256, "sc1", (5, 33)),
+               ("bf16", 4096, 16, 256, "nt", (33, 5)))
+TdCase = namedtuple("TdCase", "id kind K nvec entry grid_cap pw fuse tile")
+# quiet NaNs in everything of the tiled buffer that is no client's element [0, M)
+POISON = {"f32": 0x7FC5A5A5, "bf16": 0x7FC5}
+# The fp32 poison is the output sentinel's pattern, and a NaN keeps its payload through x * w and
+# acc + p: a pad element that reached the guard band would put the sentinel back.  The tiled cases
+# guard their outputs with another quiet NaN.
+TILED_GUARD = 0x7FE1B2B2
+
+
+def _tiled_cases():
+    out = []
+    for kind, tile, vpt, threads, store, Ks in TILED_TILES:
+        def add(K, tag, nvec, entry="main", cap=0, pw=False, fuse=1):
+            out.append(TdCase(f"fa-{kind}-tiled{tile}-{store}-K{K}-{tag}", kind, K, nvec, entry, cap, pw, fuse, tile))
+
+        for K in Ks:
+            add(K, "r0", 2 * tile)
+            add(K, "r37-pw", 2 * tile + 37, pw=True)
+            add(K, "rbig", 2 * tile + (vpt - 1) * threads + 100)
+            add(K, "cap3-pw", 4 * tile + 37, cap=3, pw=True)  # five tiles over three workgroups
+            add(K, "r37-chain", 2 * tile + 37, "chain")
+        add(Ks[0], "r37-unfused", 2 * tile + 37, pw=True, fuse=0)
+    return out
+
+
+def _tiled_small_cases():
+    """The smallest buckets: everything scalar remainder (M < L), one vector, one tile and its
+    neighbours.  nvec is not used: M is given."""
+    out = []
+    for kind, tile, vpt, threads, store, Ks in TILED_TILES:
+        L = L_OF[kind]
+        for K in (1, 5):
+            for tag, M in (("M1", 1), ("Lm1", L - 1), ("L", L), ("Lp1", L + 1), ("TLm1", tile * L - 1),
+                           ("TL", tile * L), ("TLp1", tile * L + 1)):
+                out.append((f"fa-{kind}-tiled{tile}-{store}-K{K}-small-{tag}", kind, tile, K, M))
+    return out
+
+
+TILED_CASES = _tiled_cases()
+TILED_SMALL_CASES = _tiled_small_cases()
+
+
+def _tile_of(c) -> int:
+    if isinstance(c, TdCase):
+        return c.tile
     shape = c.id.split("-")[2]
     vpt = int(shape.split("x")[0])
     return vpt * (512 if (c.kind == "f32" and vpt == 16) else 256)
@@ -225,7 +289,8 @@ SCAFFOLD_CASES = _scaffold_cases()
 # the read-stream probes and the fp64 flat gather: no reduction, but shipped and launched nowhere else
 MISC_CASES = ["misc-read-probe-stream", "misc-read-probe-tile-4", "misc-read-probe-tile-8", "misc-read-probe-tile-16",
               "misc-flat-gather-f64"]
-CASE_IDS = [c.id for c in FEDAVG_CASES] + [c.id for c in SCAFFOLD_CASES] + MISC_CASES
+CASE_IDS = ([c.id for c in FEDAVG_CASES] + [c.id for c in SCAFFOLD_CASES] + MISC_CASES
+            + [c.id for c in TILED_CASES] + [c[0] for c in TILED_SMALL_CASES])
 assert len(set(CASE_IDS)) == len(CASE_IDS)
 
 
@@ -318,7 +383,7 @@ def fedavg_rows():
 
     def get(kind):
         if kind not in held:
-            held[kind] = _Rows(torch, kind, [c for c in FEDAVG_CASES if c.kind == kind])
+            held[kind] = _Rows(torch, kind, [c for c in FEDAVG_CASES + TILED_CASES if c.kind == kind])
         return held[kind]
 
     yield get
@@ -445,15 +510,18 @@ SENTINEL = {2: 0x7E5A, 4: 0x7FC5A5A5, 8: 0x7FF8A5A5A5A5A5A5}  # quiet NaN patter
 GUARD = 64
 
 
-def _sentinel_buffer(torch, n: int, dtype):
+def _sentinel_buffer(torch, n: int, dtype, pattern=None):
     nb = torch.empty(0, dtype=dtype).element_size()
-    return torch.full((n + GUARD,), SENTINEL[nb], dtype=_int_dtype(torch, nb), device=DEV).view(dtype)
+    pattern = SENTINEL[nb] if pattern is None else pattern
+    return torch.full((n + GUARD,), pattern, dtype=_int_dtype(torch, nb), device=DEV).view(dtype)
 
 
-def _assert_guard(torch, buf, n: int, what: str):
+def _assert_guard(torch, buf, n: int, what: str, pattern=None):
     nb = buf.element_size()
     tail = buf.view(_int_dtype(torch, nb))[n:]
-    assert bool((tail == SENTINEL[nb]).all()), f"{what}: elements at and beyond M were written"
+    hit = torch.nonzero(tail != (SENTINEL[nb] if pattern is None else pattern)).flatten()
+    assert hit.numel() == 0, (f"{what}: elements at and beyond M were written, first at M + {int(hit[0])}: "
+                              f"{buf[n + int(hit[0])].item()!r}")
 
 
 def _assert_equal_bits(torch, got, ref, what: str):
@@ -557,6 +625,138 @@ def test_fedavg_product_kernel(case, fedavg_rows):
                 assert int(out.view(_int_dtype(torch, out.element_size()))[col]) == 0, (case.id, col)
                 checked += 1
         assert checked, "no all -0 column left in this case's inputs"
+
+
+# =============================================================================================
+# FedAvg over tile-interleaved buckets
+# =============================================================================================
+def _tiled_buffer(torch, kind: str, xi, K: int, M: int, T: int):
+    """The layout include/fedagg.h publishes, restated: tile t of client k at 16-B vector
+    (t * K + k) * T of the buffer, every tile T vectors, the last one padded -- a [tiles, K, T * L]
+    array whose [:, k, :] holds client k.  ``xi``: [>= K, >= M] stored bit patterns on the device.
+    Only elements [0, M) of each client are copied in; the rest of the last tile, in every client,
+    stays a quiet NaN, so one pad read that reaches an output turns it NaN."""
+    L = L_OF[kind]
+    TL = T * L
+    tiles = -(-(-(-M // L)) // T)
+    nb = xi.element_size()
+    buf = torch.full((tiles * K * TL,), POISON[kind], dtype=_int_dtype(torch, nb), device=DEV)
+    view = buf.view(tiles, K, TL)
+    n_full = M // TL
+    for k in range(K):
+        if n_full:
+            view[:n_full, k, :] = xi[k, : n_full * TL].view(n_full, TL)
+        if M % TL:
+            view[n_full, k, : M % TL] = xi[k, n_full * TL: M]
+    assert int((buf == POISON[kind]).sum()) >= K * (tiles * TL - M)
+    return buf
+
+
+def _c_weights(w, K):
+    return (ctypes.c_float * K)(*[float(v) for v in w])
+
+
+@pytest.mark.parametrize("case", TILED_CASES, ids=[c.id for c in TILED_CASES])
+def test_fedavg_tiled_product_kernel(case, fedavg_rows):
+    import torch
+
+    from substrafl_amd import _native
+    from substrafl_amd.engine import TiledFedAvgPlan, fedavg_weights
+
+    lib = _native.load()
+    rows = fedavg_rows(case.kind)
+    kind, K, M, T = case.kind, case.K, _M(case), case.tile
+    x = rows.x[:K]
+    ns = rows.ns[:K]
+    w = fedavg_weights(ns, kind)
+    idx = _pw_idx(case) if case.pw else []
+    assert case.entry == "main" or not idx
+    assert M < HOST_REF_MAX and K <= _native.FEDAGG_KCHUNK  # host references; one fedavg_kernel launch
+    if idx:
+        assert (idx[2] // L_OF[kind]) // T >= 1  # a numel == 1 index behind tile 0: its place depends on K
+    buf = _tiled_buffer(torch, kind, x.view(_int_dtype(torch, x.element_size())), K, M, T)
+
+    seed = None
+    out = _sentinel_buffer(torch, M, torch.float32, TILED_GUARD)
+    if case.entry == "chain":  # the accumulator the call continues: a partial sum of other rows, -0 in front
+        seed = (rows.x[K_MAX - 1, :M].to(torch.float32) * 0.25).contiguous()
+        seed[:8] = -0.0
+        out[:M] = seed
+        _assert_equal_bits(torch, out[:M], seed, case.id + " (seed)")
+    ws = None
+    if idx and not case.fuse:
+        ws = torch.empty(max(16, lib.fedagg_pairwise_ws_bytes(K, len(idx), 8)), dtype=torch.uint8, device=DEV)
+    _sync(torch)
+
+    _native.tune(grid_cap=case.grid_cap, fuse_pairwise=case.fuse)
+    try:
+        if case.entry == "main":
+            TiledFedAvgPlan(kind, buf, K, w, M, out, idx, ws, tv=T).launch()
+        else:
+            rc = getattr(lib, f"fedagg_fedavg_chain_tiled_{kind}")(buf.data_ptr(), _c_weights(w, K), K, M, T, 0,
+                                                                   out.data_ptr(), None)
+            assert rc == 0, lib.fedagg_last_error()
+        _sync(torch)
+    finally:
+        _native.tune(**RESET)
+
+    xs = _host_rows(torch, x, kind, K, M)
+    if seed is None:
+        ref_np = _oracle_layers(xs, ns, idx)
+    else:
+        ref_np = _np_sequential(xs, w, seed.cpu().numpy())
+    ref = torch.from_numpy(np.ascontiguousarray(ref_np)).to(DEV)
+    assert ref.dtype == torch.float32 and ref.numel() == M and not bool(torch.isnan(ref).any())
+    _assert_equal_bits(torch, out[:M], ref, case.id)
+    _assert_guard(torch, out, M, case.id, TILED_GUARD)
+    if seed is None:  # an all -0 column sums to +0.0 (the accumulator starts from +0.0)
+        xi = x.view(_int_dtype(torch, x.element_size()))
+        neg0 = _signed(NEG_ZERO[kind], x.element_size())
+        checked = 0
+        for pos, n, zero in _planted_positions(kind, case.nvec, T):
+            col = pos + n - 1
+            if zero and n > 0 and col not in idx and bool((xi[:, col] == neg0).all()):
+                assert int(out.view(torch.int32)[col]) == 0, (case.id, col)
+                checked += 1
+        assert checked, "no all -0 column left in this case's inputs"
+
+
+@pytest.mark.parametrize("case", TILED_SMALL_CASES, ids=[c[0] for c in TILED_SMALL_CASES])
+def test_fedavg_tiled_smallest_buckets(case):
+    """M = 1, L - 1 (no vector at all: one workgroup, everything scalar remainder), L, L + 1 and
+    one tile -1 / 0 / +1 elements, for 1 and 5 clients, against NumPy in client order; from three
+    elements on, M - 1 is a numel == 1 index (the oracle)."""
+    import torch
+
+    from substrafl_amd import _native
+    from substrafl_amd.engine import TiledFedAvgPlan, fedavg_weights
+
+    assert torch.cuda.is_available(), "GPU tests need an MI355X"
+    cid, kind, T, K, M = case
+    rng = np.random.default_rng(sum(map(ord, cid)))
+    stored = rng.standard_normal((K, M)).astype(np.float32).view(np.uint32)
+    if kind == "bf16":
+        stored = (stored >> np.uint32(16)).astype(np.uint16)
+    n_e = min(M, len(EDGES[kind]))
+    stored[: min(3, K), :n_e] = _plant_block(kind, 3, n_e, M % 7)[: min(3, K)]
+    stored = np.ascontiguousarray(stored)
+    ns = [int(v) for v in rng.integers(100, 10000, K)]
+    w = fedavg_weights(ns, kind)
+    idx = [M - 1] if M >= 3 else []
+    xi = torch.from_numpy(stored.view({2: np.int16, 4: np.int32}[stored.itemsize])).to(DEV)
+    buf = _tiled_buffer(torch, kind, xi, K, M, T)
+    out = _sentinel_buffer(torch, M, torch.float32, TILED_GUARD)
+    _sync(torch)
+    TiledFedAvgPlan(kind, buf, K, w, M, out, idx, tv=T).launch()
+    _sync(torch)
+
+    xs = _upcast_np(stored, kind)
+    ref_np = _np_sequential(xs, w, None)
+    if idx:
+        ref_np[M - 1] = _oracle_layers(xs, ns, idx)[M - 1]
+    assert ref_np.dtype == np.float32 and not np.isnan(ref_np).any()
+    _assert_equal_bits(torch, out[:M], torch.from_numpy(ref_np).to(DEV), cid)
+    _assert_guard(torch, out, M, cid, TILED_GUARD)
 
 
 # =============================================================================================

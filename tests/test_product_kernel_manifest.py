@@ -52,16 +52,16 @@ def test_manifest_keys_are_the_committed_kernel_list(manifest, committed):
                                              sorted(set(manifest) - set(committed)))
     for name, e in manifest.items():
         assert len(e) == 1 and next(iter(e)) in ("rows", "covered_by", "unreachable"), name
-        tiled = _family(name) == "fedavg_kernel" and not name.endswith(", 0>")  # tile-interleaved buckets
         if "unreachable" in e:
             args = name[name.index("<") + 1: -1].split(", ")
             assert _family(name) == "scaffold_bucket_kernel" and args[6] == "2", name  # the PH = 2 pair
             assert "sc_2l" in e["unreachable"] and "FEDAGG_TUNING" in e["unreachable"]
-        elif _family(name) in ROW_FAMILIES and not tiled and name not in (
+        elif _family(name) in ROW_FAMILIES and name not in (
                 "scaffold_rows_kernel<KF16, 2, 4, false>", "scaffold_rows_kernel<KBF16, 2, 4, false>"):
+            # the tile-interleaved fedavg_kernel instantiations (last argument != 0) included
             assert e.get("rows"), f"{name} needs rows"
         elif "covered_by" in e:
-            assert tiled or _family(name) in COVERED_BY_OK or _family(name) == "scaffold_rows_kernel", name
+            assert _family(name) in COVERED_BY_OK or _family(name) == "scaffold_rows_kernel", name
     assert sum("unreachable" in e for e in manifest.values()) == 2
 
 

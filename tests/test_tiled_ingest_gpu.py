@@ -57,6 +57,46 @@ def test_stage_tiled_row_places_like_stage_tiled(torch_gpu, K, tv, chunk):
         s.close()
 
 
+@pytest.mark.parametrize("store,tv,k", [(np.uint32, 2048, 0), (np.uint32, 2048, 2), (np.uint32, 2048, 4),
+                                         (np.uint16, 4096, 2)])
+def test_stage_tiled_row_writes_only_its_own_tiles(torch_gpu, store, tv, k):
+    """Staging client k of 5 leaves every other client's tiles, and a guard tile behind the buffer,
+    as they were (a sentinel byte pattern); the chunk is no divisor of the row, so the last 2-D copy
+    is shorter than the others.  The pad of client k's own last tile is unspecified.  The layout is
+    include/fedagg.h's: tile t of client k at tile (t * K + k).  2-byte rows at the bf16 tile."""
+    from substrafl_amd.runtime import Session
+
+    K, tile_bytes = 5, tv * 16
+    te = tile_bytes // np.dtype(store).itemsize  # elements per tile
+    tiles, last = 8, 1237
+    M = (tiles - 1) * te + last
+    rng = np.random.default_rng(100 * tv + k)
+    row = rng.integers(0, np.iinfo(store).max, M, dtype=store, endpoint=True)
+    segs = [row[:20_001], row[20_001:20_002], row[20_002:]]  # ragged segments
+    chunk = 3 * tile_bytes + 4096  # three tiles per copy: 3 + 3 + 2
+    assert (M * row.itemsize) % chunk and chunk >= 1 << 16
+    sent = 0xA5
+    n = (tiles * K + 1) * te  # one guard tile behind
+    s = Session(0, threads=4)
+    try:
+        s.set("chunk_bytes", chunk)
+        d = s.buffer(0, n * row.itemsize)
+        s.memset(d, sent, n * row.itemsize)
+        s.stage_tiled_row(d, tile_bytes, K, k, segs)
+        got = np.empty(n, store)
+        s.fetch(d, got)
+    finally:
+        s.close()
+    fill = np.frombuffer(bytes([sent]) * row.itemsize, store)[0]
+    body, guard = got[: tiles * K * te].reshape(tiles, K, te), got[tiles * K * te:]
+    assert np.array_equal(body[:, k, :].reshape(-1)[:M], row)
+    for other in range(K):
+        if other != k:
+            bad = np.argwhere(body[:, other, :] != fill)
+            assert bad.size == 0, f"client {other}: {len(bad)} elements overwritten, first (tile, element) {bad[0]}"
+    assert np.all(guard == fill), "the tile behind the buffer was written"
+
+
 def test_stage_tiled_row_rejects_and_recovers(torch_gpu):
     from substrafl_amd._native import NativeLibraryError
     from substrafl_amd.engine import tiled_elems, tiled_index
