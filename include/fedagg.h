@@ -577,8 +577,10 @@ int fedagg_session_stage_tiled_row(fedagg_session* s, void* d_dst, uint64_t tile
  * fedagg_session_stage); ONE copy -- bytes [byte_lo, byte_hi) of row 0 -- is staged to d_dst, the
  * same bytes of rows 1..K-1 are compared with it by value on the pack workers (+0 == -0,
  * NaN == NaN; byte-identical stretches skipped) and the number of mismatching elements is written
- * to *mismatches.  kind: FEDAGG_F32 or FEDAGG_F64 (every segment of that element type; the range
- * element-aligned).  Replaces K-1 PCIe copies plus the device check (fedagg_equal_count_*).
+ * to *mismatches.  kind: FEDAGG_F16, FEDAGG_BF16, FEDAGG_F32 or FEDAGG_F64 (every segment of that
+ * element type; the range element-aligned).  The 16-bit kinds are compared as bit patterns: equal
+ * bits, two zeros ((b & 0x7FFF) == 0) or two NaNs ((b & 0x7FFF) above 0x7C00 for fp16, 0x7F80 for
+ * bf16) are equal.  Replaces K-1 PCIe copies plus the device check (fedagg_equal_count_*).
  * d_dst may be NULL: compare only (rows already staged, e.g. while the inputs are still loading). */
 int fedagg_session_stage_check(fedagg_session* s, void* d_dst, int K, int nseg, const void* const* h_seg,
                                const uint64_t* seg_bytes, uint64_t byte_lo, uint64_t byte_hi, int kind,
@@ -655,6 +657,33 @@ int fedagg_multi_fedavg_f64(fedagg_multi* m, int K, int nseg, const void* const*
 /* fp16 buckets: h_w and h_out hold fp16 bit patterns (fedagg_fedavg_f16's semantics, NumPy's half loops) */
 int fedagg_multi_fedavg_f16(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
                             const uint16_t* h_w, const uint64_t* h_idx, int P, uint16_t* h_out);
+/* Scaffold on the same plan: ONE bucket per call, as fedagg_scaffold_bucket, over host rows -- an
+ * aggregation is two calls.  Replaces scaffold.py:293 (phase 0, the delta bucket: lr * sum_k w_k *
+ * delta_k), scaffold.py:262-263 (phase 1, the control-variate bucket: sum_k w_k * cv_k, then + c
+ * LAST) and scaffold.py:193-196 (the equality of the clients' c, as a mismatch count).  Every
+ * output element is computed by fedagg_scaffold_bucket on the sub-range that owns it, so h_out is
+ * bit-identical to one whole-range call (f32 / f64 rows: to fedagg_scaffold_f32 / _f64).
+ *   h_rows: K clients x nseg host segments of row_kind (FEDAGG_F16 / _BF16 / _F32 / _F64) elements,
+ *   M = sum(seg_bytes) / element size; h_w the K fp64 weights n_k / n; h_idx the P flat indices of
+ *   numel == 1 tensors; h_out M doubles of host memory.
+ *   phase 0 reads neither the c arguments nor mismatches (which may be NULL).
+ *   phase 1: h_c holds Kc host copies of c (Kc x c_nseg segments, c_seg_bytes totalling M elements
+ *   of c_kind: any of the four kinds next to 16-bit rows, row_kind next to f32 / f64 rows).
+ *   Kc == 1: the copy is staged, nothing is checked.  Kc == K: copy 0 is staged and copies 1..K-1
+ *   are compared with it by value on the pack workers, range by range
+ *   (fedagg_session_stage_check); *mismatches receives the mismatching elements over all copies.
+ *   h_out is written whatever the count.
+ * Each element of a sub-range takes K * row size + 8 bytes of HBM (+ the c element in phase 1).
+ * Without "max_shard_bytes" the budget of a sub-range is 85 % of the device's free HBM, read once
+ * per device before the shard threads start, divided by the shards on that device, less the
+ * numel == 1 workspace.  M == 0: FEDAGG_OK.  Bad arguments (NULL m, K <= 0, an unknown kind, a c
+ * kind breaking the rule, Kc not 1 or K, a segment that is not a whole number of elements, a c row
+ * that does not total M elements, an index >= M, NULL h_out, NULL mismatches with Kc == K) return
+ * FEDAGG_EINVAL before any HIP call.  Blocking; the caller's current device is unchanged. */
+int fedagg_multi_scaffold_bucket(fedagg_multi* m, int phase, int K, int nseg, const void* const* h_rows,
+                                 const uint64_t* seg_bytes, int row_kind, const double* h_w, double lr, int Kc,
+                                 int c_nseg, const void* const* h_c, const uint64_t* c_seg_bytes, int c_kind,
+                                 const uint64_t* h_idx, int P, double* h_out, uint64_t* mismatches);
 /* shard g: its device, the GPU's NUMA node (-1 unknown), pack workers, CPUs they are bound to, and
  * of the last call its element range [lo, hi) and the sub-ranges it streamed (any pointer NULL) */
 int fedagg_multi_shard_info(fedagg_multi* m, int g, int* device, int* numa_node, int* threads, int* ncpus,

@@ -123,11 +123,30 @@ inline uint64_t count_value_mismatch(const char* x, const char* r, uint64_t n) {
   return bad;
 }
 
-// Mismatching elements (size esz: 4 = float, 8 = double) between bytes [a, b) of two rows given
-// as segment lists of the same lengths.  Byte-identical stretches are skipped with memcmp; only
-// a differing 4 KiB block is compared by value.  Segment and range bounds are element-aligned.
+// The two 16-bit element kinds of the value check (`half` below; 0 = esz alone names the type).
+enum { kHalfNone = 0, kHalfF16 = 1, kHalfBF16 = 2 };
+
+// The same for n 16-bit elements, as integer compares on the bit patterns: equal when the bits
+// are equal, both are zero ((b & 0x7FFF) == 0) or both are NaN ((b & 0x7FFF) > inf_bits, the
+// pattern of +inf: 0x7C00 for fp16, 0x7F80 for bf16).
+inline uint64_t count_value_mismatch16(const char* x, const char* r, uint64_t n, uint16_t inf_bits) {
+  uint64_t bad = 0;
+  for (uint64_t i = 0; i < n; ++i) {
+    uint16_t a, b;
+    memcpy(&a, x + i * 2, 2);
+    memcpy(&b, r + i * 2, 2);
+    const uint16_t ma = a & 0x7FFF, mb = b & 0x7FFF;
+    bad += !((a == b) || ((ma | mb) == 0) || (ma > inf_bits && mb > inf_bits));
+  }
+  return bad;
+}
+
+// Mismatching elements (size esz: 4 = float, 8 = double; 2 = fp16 or bf16 as `half` says) between
+// bytes [a, b) of two rows given as segment lists of the same lengths.  Byte-identical stretches
+// are skipped with memcmp; only a differing 4 KiB block is compared by value.  Segment and range
+// bounds are element-aligned.
 inline uint64_t count_mismatch_range(const void* const* x, const void* const* ref, const uint64_t* len, int nseg,
-                                     uint64_t a, uint64_t b, int esz) {
+                                     uint64_t a, uint64_t b, int esz, int half = kHalfNone) {
   uint64_t off = 0, bad = 0;
   for (int i = 0; i < nseg && off < b; ++i) {
     const uint64_t s0 = off, s1 = off + len[i];
@@ -140,8 +159,9 @@ inline uint64_t count_mismatch_range(const void* const* x, const void* const* re
     for (uint64_t u = 0; u < hi - lo; u += 4096) {
       const uint64_t n = std::min<uint64_t>(4096, hi - lo - u);
       if (!memcmp(px + u, pr + u, n)) continue;
-      bad += esz == 8 ? count_value_mismatch<double>(px + u, pr + u, n / 8)
-                      : count_value_mismatch<float>(px + u, pr + u, n / 4);
+      bad += half ? count_value_mismatch16(px + u, pr + u, n / 2, half == kHalfBF16 ? 0x7F80 : 0x7C00)
+             : esz == 8 ? count_value_mismatch<double>(px + u, pr + u, n / 8)
+                        : count_value_mismatch<float>(px + u, pr + u, n / 4);
     }
   }
   return bad;
@@ -166,11 +186,12 @@ struct Ring {
   int size() const { return (int)slot.size(); }
 };
 
-// Value check of bytes [byte_lo, byte_lo + row) of rows 1..K-1 against row 0 (esz-byte elements),
-// in 1 MiB pieces of the row on the pool; returns the number of mismatching elements.  Touches
-// nothing but the pool and the caller's segments, so it may run beside a staging call.
+// Value check of bytes [byte_lo, byte_lo + row) of rows 1..K-1 against row 0 (esz-byte elements;
+// half: kHalfF16 / kHalfBF16 for 2-byte ones), in 1 MiB pieces of the row on the pool; returns the
+// number of mismatching elements.  Touches nothing but the pool and the caller's segments, so it
+// may run beside a staging call.
 inline uint64_t check_rows(Pool& pool, const void* const* h_seg, const uint64_t* seg_bytes, int nseg, int K,
-                           uint64_t byte_lo, uint64_t row, int esz) {
+                           uint64_t byte_lo, uint64_t row, int esz, int half = kHalfNone) {
   const uint64_t piece = 1ull << 20;
   const uint64_t npieces = (K >= 2 && row) ? (row + piece - 1) / piece : 0;
   std::atomic<uint64_t> bad{0};
@@ -180,7 +201,7 @@ inline uint64_t check_rows(Pool& pool, const void* const* h_seg, const uint64_t*
     Done* d = &cdone[p];
     pool.submit([=, &bad] {
       uint64_t n = 0;
-      for (int k = 1; k < K; ++k) n += count_mismatch_range(h_seg + (size_t)k * nseg, h_seg, seg_bytes, nseg, a, b, esz);
+      for (int k = 1; k < K; ++k) n += count_mismatch_range(h_seg + (size_t)k * nseg, h_seg, seg_bytes, nseg, a, b, esz, half);
       bad.fetch_add(n, std::memory_order_relaxed);
       d->set();
     });
@@ -236,12 +257,13 @@ int ring_stage(Eng& eng, Pool& pool, Ring& ring, uint64_t units, bool two_queues
 
 // K rows of nseg host segments -> d_dst + k * ld_bytes, bytes [byte_lo, byte_lo + row) of each
 // row.  check_esz > 0: only row 0 is staged, rows 1..K-1 are compared with it by value on the
-// host (mismatching elements added to *mismatches) -- the server-control-variate check of
-// scaffold.py:193-196 done while the bytes are in host memory anyway, one copy over PCIe.
+// host (mismatching elements added to *mismatches; check_half names the kind of 2-byte elements)
+// -- the server-control-variate check of scaffold.py:193-196 done while the bytes are in host
+// memory anyway, one copy over PCIe.
 template <class Eng>
 int stage_pipeline(Eng& eng, Pool& pool, Ring& ring, const void* const* h_seg, const uint64_t* seg_bytes, int nseg,
                    int K, uint64_t byte_lo, uint64_t row, char* d_dst, uint64_t ld_bytes, bool two_queues,
-                   int check_esz = 0, uint64_t* mismatches = nullptr) {
+                   int check_esz = 0, uint64_t* mismatches = nullptr, int check_half = kHalfNone) {
   const uint64_t cb = ring.chunk_bytes;
   const int Ks = check_esz ? 1 : K;
   const uint64_t per_row = row ? (row + cb - 1) / cb : 0;  // unit u: chunk u % per_row of row u / per_row
@@ -256,7 +278,7 @@ int stage_pipeline(Eng& eng, Pool& pool, Ring& ring, const void* const* h_seg, c
         return eng.h2d(q, d_dst + (u / per_row) * ld_bytes + a, slot, std::min(row, a + cb) - a);
       });
   if (rc || !check_esz || K < 2) return rc;
-  const uint64_t bad = check_rows(pool, h_seg, seg_bytes, nseg, K, byte_lo, row, check_esz);
+  const uint64_t bad = check_rows(pool, h_seg, seg_bytes, nseg, K, byte_lo, row, check_esz, check_half);
   if (mismatches) *mismatches += bad;
   return 0;
 }

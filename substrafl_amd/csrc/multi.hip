@@ -17,6 +17,11 @@
 // Every output element is computed by the single-GPU kernel's arithmetic, so the result is bit-
 // identical to fedagg_fedavg_* over the whole range and to the reference (fed_avg.py:217-222): no
 // collective, no re-association.
+//
+// Scaffold runs on the same plan one bucket per call (fedagg_multi_scaffold_bucket): rows of any
+// float kind staged as they are, fedagg_scaffold_bucket per sub-range, and the clients' copies of c
+// compared on the pack workers while copy 0 of the sub-range is staged (scaffold.py:193-196,
+// 262-263, 293).
 
 #include <hip/hip_runtime.h>
 
@@ -43,7 +48,7 @@ constexpr uint64_t kShardAlign = 512;     // elements: every shard row starts 25
 constexpr uint64_t kRowAlignBytes = 256;  // row stride of a staged [K, ld] bucket (layout.ROW_ALIGN_BYTES)
 constexpr double kHeadroom = 0.85;        // share of free HBM one sub-range may take (multi_device.HBM_HEADROOM)
 constexpr int kPackThreadsCap = 32;       // pack workers per GPU past which staging stops scaling
-enum { kSlotBucket = 0, kSlotOut = 1, kSlotWs = 2 };
+enum { kSlotBucket = 0, kSlotOut = 1, kSlotWs = 2, kSlotC = 3 };  // kSlotC: Scaffold's staged copy of c
 
 int fail(const std::string& msg) {
   fedagg_internal::set_error(msg.c_str());
@@ -114,7 +119,7 @@ struct Shard {
   int numa_node = -1;
   int threads = 0;
   std::vector<int> cpus;
-  uint64_t held[3] = {0, 0, 0};  // bytes of the session buffer slots this engine grew
+  uint64_t held[4] = {0, 0, 0, 0};  // bytes of the session buffer slots this engine grew
   // the last call
   uint64_t lo = 0, hi = 0;
   int ranges = 0;
@@ -279,6 +284,84 @@ int multi_fedavg(fedagg_multi* m, int K, int nseg, const void* const* h_seg, con
   return FEDAGG_OK;
 }
 
+// ---- Scaffold, one bucket per call (fedagg_multi_scaffold_bucket) ----------------------------
+
+uint64_t kind_bytes(int kind) {  // 0: not one of the four float kinds
+  switch (kind) {
+    case FEDAGG_F16:
+    case FEDAGG_BF16: return 2;
+    case FEDAGG_F32: return 4;
+    case FEDAGG_F64: return 8;
+    default: return 0;
+  }
+}
+
+struct ScaffoldCall {
+  int phase, K, nseg, row_kind, Kc, c_nseg, c_kind;
+  const void* const* h_rows;
+  const uint64_t* seg_bytes;
+  const double* h_w;
+  double lr;
+  const void* const* h_c;
+  const uint64_t* c_seg_bytes;
+  std::vector<uint64_t> idx;
+  double* h_out;
+  size_t ws_bytes;
+  uint64_t esz, c_esz;
+};
+
+// One shard's sub-ranges of one Scaffold bucket, in order; `budget` is the HBM one sub-range may take.
+int run_scaffold_shard(Shard& sh, const ScaffoldCall& a, uint64_t budget, uint64_t* mismatches) {
+  sh.ranges = 0;
+  sh.stage_s = sh.kernel_fetch_s = 0;
+  if (sh.hi <= sh.lo) return FEDAGG_OK;
+  int rc = fedagg_session_activate(sh.s);
+  if (rc) return rc;
+  const uint64_t per_elem = (uint64_t)a.K * a.esz + 8 + (a.phase == 1 ? a.c_esz : 0);
+  const uint64_t step = std::max(kShardAlign, budget / per_elem / kShardAlign * kShardAlign);  // multi_device._split
+  std::vector<const void*> rows(a.K);
+  std::vector<uint64_t> pw;
+  for (uint64_t lo = sh.lo; lo < sh.hi; lo += step) {
+    const uint64_t hi = std::min(sh.hi, lo + step), n = hi - lo, ld = row_ld(n, a.esz);
+    const double t0 = now_s();
+    void *d_bucket = nullptr, *d_out = nullptr, *d_ws = nullptr, *d_c = nullptr;
+    if ((rc = shard_buffer(sh, kSlotBucket, (uint64_t)a.K * ld * a.esz, &d_bucket))) return rc;
+    if ((rc = fedagg_session_stage_range(sh.s, d_bucket, ld * a.esz, a.K, a.nseg, a.h_rows, a.seg_bytes, lo * a.esz,
+                                         hi * a.esz)))
+      return rc;
+    if (a.phase == 1) {
+      const uint64_t ldc = row_ld(n, a.c_esz) * a.c_esz;
+      if ((rc = shard_buffer(sh, kSlotC, ldc, &d_c))) return rc;
+      if (a.Kc == a.K) {  // copy 0 staged, the others compared with it on the pack workers
+        uint64_t bad = 0;
+        if ((rc = fedagg_session_stage_check(sh.s, d_c, a.K, a.c_nseg, a.h_c, a.c_seg_bytes, lo * a.c_esz,
+                                             hi * a.c_esz, a.c_kind, &bad)))
+          return rc;
+        *mismatches += bad;
+      } else if ((rc = fedagg_session_stage_range(sh.s, d_c, ldc, 1, a.c_nseg, a.h_c, a.c_seg_bytes, lo * a.c_esz,
+                                                  hi * a.c_esz))) {
+        return rc;
+      }
+    }
+    const double t1 = now_s();
+    if ((rc = shard_buffer(sh, kSlotOut, row_ld(n, 8) * 8, &d_out))) return rc;
+    if ((rc = shard_buffer(sh, kSlotWs, a.ws_bytes, &d_ws))) return rc;
+    pw.clear();
+    for (uint64_t i : a.idx)
+      if (i >= lo && i < hi) pw.push_back(i - lo);
+    for (int k = 0; k < a.K; ++k) rows[k] = static_cast<const char*>(d_bucket) + (uint64_t)k * ld * a.esz;
+    if ((rc = fedagg_scaffold_bucket(rows.data(), a.row_kind, a.h_w, a.K, n, a.phase, d_c, a.c_kind, a.lr,
+                                     pw.empty() ? nullptr : pw.data(), (int)pw.size(), d_ws,
+                                     static_cast<double*>(d_out), fedagg_session_stream(sh.s))))
+      return rc;
+    if ((rc = fedagg_session_fetch(sh.s, d_out, a.h_out + lo, n * 8))) return rc;
+    sh.stage_s += t1 - t0;
+    sh.kernel_fetch_s += now_s() - t1;
+    ++sh.ranges;
+  }
+  return FEDAGG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -378,6 +461,123 @@ int fedagg_multi_fedavg_f64(fedagg_multi* m, int K, int nseg, const void* const*
 int fedagg_multi_fedavg_f16(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
                             const uint16_t* h_w, const uint64_t* h_idx, int P, uint16_t* h_out) {
   return multi_fedavg<uint16_t>(m, K, nseg, h_seg, seg_bytes, h_w, h_idx, P, h_out, "fedagg_multi_fedavg_f16");
+}
+
+int fedagg_multi_scaffold_bucket(fedagg_multi* m, int phase, int K, int nseg, const void* const* h_rows,
+                                 const uint64_t* seg_bytes, int row_kind, const double* h_w, double lr, int Kc,
+                                 int c_nseg, const void* const* h_c, const uint64_t* c_seg_bytes, int c_kind,
+                                 const uint64_t* h_idx, int P, double* h_out, uint64_t* mismatches) {
+  const std::string name = "fedagg_multi_scaffold_bucket";
+  // every argument check comes before the first HIP call
+  if (K <= 0) return fail(name + ": K must be > 0");
+  if (phase != 0 && phase != 1) return fail(name + ": phase must be 0 or 1");
+  ScaffoldCall a{};
+  a.esz = kind_bytes(row_kind);
+  if (!a.esz) return fail(name + ": unknown row kind");
+  if (nseg < 0 || (nseg > 0 && (!h_rows || !seg_bytes)) || !h_w || P < 0 || (P > 0 && !h_idx))
+    return fail(name + ": invalid argument");
+  uint64_t row = 0;
+  for (int i = 0; i < nseg; ++i) {
+    if (seg_bytes[i] % a.esz) return fail(name + ": segment not a whole number of elements");
+    row += seg_bytes[i];
+  }
+  const uint64_t M = row / a.esz;
+  if (phase == 1) {
+    a.c_esz = kind_bytes(c_kind);
+    if (!a.c_esz) return fail(name + ": unknown c kind");
+    if ((row_kind == FEDAGG_F32 || row_kind == FEDAGG_F64) && c_kind != row_kind)
+      return fail(name + ": c kind must equal the kind of f32 / f64 rows");
+    if (Kc != 1 && Kc != K) return fail(name + ": Kc must be 1 or K");
+    if (c_nseg < 0 || (c_nseg > 0 && (!h_c || !c_seg_bytes))) return fail(name + ": invalid c argument");
+    uint64_t c_row = 0;
+    for (int i = 0; i < c_nseg; ++i) {
+      if (c_seg_bytes[i] % a.c_esz) return fail(name + ": c segment not a whole number of elements");
+      c_row += c_seg_bytes[i];
+    }
+    if (c_row / a.c_esz != M) return fail(name + ": a c row does not total M elements");
+    for (int k = 0; k < Kc; ++k)
+      for (int i = 0; i < c_nseg; ++i)
+        if (!h_c[(size_t)k * c_nseg + i] && c_seg_bytes[i]) return fail(name + ": NULL c segment");
+    if (Kc == K && !mismatches) return fail(name + ": NULL mismatches with Kc == K");
+  }
+  a.idx.assign(h_idx, h_idx + P);
+  for (uint64_t i : a.idx)
+    if (i >= M) return fail(name + ": numel == 1 index out of range");
+  if (!h_out) return fail(name + ": NULL h_out");
+  if (!m) return fail(name + ": NULL engine");
+  if (phase == 1 && mismatches) *mismatches = 0;
+  if (M == 0) return FEDAGG_OK;
+  a.phase = phase, a.K = K, a.nseg = nseg, a.row_kind = row_kind;
+  a.Kc = Kc, a.c_nseg = c_nseg, a.c_kind = phase == 1 ? c_kind : FEDAGG_F64;
+  a.h_rows = h_rows, a.seg_bytes = seg_bytes, a.h_w = h_w, a.lr = lr;
+  a.h_c = h_c, a.c_seg_bytes = c_seg_bytes, a.h_out = h_out;
+  a.ws_bytes = fedagg_pairwise_ws_bytes(K, std::max(1, P), 8);
+  std::lock_guard<std::mutex> g(m->m);
+  int caller = -1;
+  (void)hipGetDevice(&caller);
+  const uint64_t G = m->shards.size();
+  uint64_t chunk = (M + G - 1) / G;  // shard_bounds(M, G), as multi_fedavg
+  chunk = (chunk + kShardAlign - 1) / kShardAlign * kShardAlign;
+  for (uint64_t gi = 0; gi < G; ++gi) {
+    m->shards[gi].lo = std::min(M, gi * chunk);
+    m->shards[gi].hi = std::min(M, (gi + 1) * chunk);
+    m->shards[gi].ranges = 0;
+  }
+  // HBM one sub-range may take.  The shard threads of one device all allocate from the same free
+  // HBM, so it is read once per distinct device here, before any of them starts, and divided by
+  // the shards on that device; the numel == 1 workspace comes off before the step is computed.
+  std::vector<uint64_t> budget(G, m->max_shard_bytes);
+  if (!m->max_shard_bytes) {
+    for (uint64_t gi = 0; gi < G; ++gi) {
+      if (budget[gi]) continue;  // filled in with an earlier shard of the same device
+      const int dev = m->shards[gi].device;
+      uint64_t free_b = 0, total_b = 0, held = 0, n_on_dev = 0;
+      const int rc = fedagg_device_memory(dev, &free_b, &total_b);
+      if (rc) {
+        const std::string e = fedagg_last_error();
+        if (caller >= 0) (void)hipSetDevice(caller);
+        fail(name + ": free HBM of device " + std::to_string(dev) + ": " + e);
+        return rc;
+      }
+      for (const Shard& sh : m->shards)
+        if (sh.device == dev) {
+          ++n_on_dev;
+          for (uint64_t h : sh.held) held += h;
+        }
+      const uint64_t share = (uint64_t)((double)(free_b + held) * kHeadroom) / n_on_dev;
+      for (uint64_t gj = gi; gj < G; ++gj)
+        if (m->shards[gj].device == dev) budget[gj] = std::max<uint64_t>(1, share - std::min<uint64_t>(share, a.ws_bytes));
+    }
+  }
+  std::vector<int> rcs(G, FEDAGG_OK);
+  std::vector<uint64_t> bad(G, 0);
+  std::vector<std::string> errs(G);
+  std::vector<std::thread> th;
+  bool spawned = true;
+  try {
+    for (uint64_t gi = 0; gi < G; ++gi)
+      th.emplace_back([&, gi] {
+        rcs[gi] = run_scaffold_shard(m->shards[gi], a, budget[gi], &bad[gi]);
+        if (rcs[gi]) errs[gi] = fedagg_last_error();  // the error text is per thread: carry it back
+      });
+  } catch (const std::exception& e) {  // no thread for a shard: the started ones finish, the call fails
+    spawned = false;
+    errs.assign(G, std::string("cannot start a shard thread: ") + e.what());
+  }
+  for (auto& t : th) t.join();
+  if (caller >= 0) (void)hipSetDevice(caller);  // the caller's later work stays on its own device
+  if (!spawned) return fail(name + ": " + errs[0]);
+  for (uint64_t gi = 0; gi < G; ++gi)
+    if (rcs[gi]) {
+      char buf[640];
+      snprintf(buf, sizeof(buf), "%s: shard %d (device %d): %s", name.c_str(), (int)gi, m->shards[gi].device,
+               errs[gi].c_str());
+      fedagg_internal::set_error(buf);
+      return rcs[gi];
+    }
+  if (phase == 1 && Kc == K)
+    for (uint64_t gi = 0; gi < G; ++gi) *mismatches += bad[gi];
+  return FEDAGG_OK;
 }
 
 int fedagg_multi_shard_info(fedagg_multi* m, int g, int* device, int* numa_node, int* threads, int* ncpus,

@@ -418,10 +418,11 @@ int stage_run_with(fedagg_session* s, Run run) {
 }
 
 int stage_run(fedagg_session* s, void* d_dst, uint64_t ld_bytes, int K, int nseg, const void* const* h_seg,
-              const uint64_t* seg_bytes, uint64_t byte_lo, uint64_t row, int check_esz, uint64_t* mismatches) {
+              const uint64_t* seg_bytes, uint64_t byte_lo, uint64_t row, int check_esz, uint64_t* mismatches,
+              int check_half = fedagg_host::kHalfNone) {
   return stage_run_with(s, [&](HipEngine& eng, bool two) {
     return fedagg_host::stage_pipeline(eng, s->workers(), s->ring, h_seg, seg_bytes, nseg, K, byte_lo, row,
-                                       static_cast<char*>(d_dst), ld_bytes, two, check_esz, mismatches);
+                                       static_cast<char*>(d_dst), ld_bytes, two, check_esz, mismatches, check_half);
   });
 }
 
@@ -479,11 +480,15 @@ int fedagg_session_stage_tiled_row(fedagg_session* s, void* d_dst, uint64_t tile
 int fedagg_session_stage_check(fedagg_session* s, void* d_dst, int K, int nseg, const void* const* h_seg,
                                const uint64_t* seg_bytes, uint64_t byte_lo, uint64_t byte_hi, int kind,
                                uint64_t* mismatches) {
-  if (!mismatches || (kind != FEDAGG_F32 && kind != FEDAGG_F64)) {
-    fedagg_internal::set_error("fedagg_session_stage_check: kind must be FEDAGG_F32 or FEDAGG_F64");
+  if (!mismatches || (kind != FEDAGG_F32 && kind != FEDAGG_F64 && kind != FEDAGG_F16 && kind != FEDAGG_BF16)) {
+    fedagg_internal::set_error(
+        "fedagg_session_stage_check: kind must be FEDAGG_F16, FEDAGG_BF16, FEDAGG_F32 or FEDAGG_F64");
     return FEDAGG_EINVAL;
   }
-  const int esz = kind == FEDAGG_F64 ? 8 : 4;
+  const int esz = kind == FEDAGG_F64 ? 8 : kind == FEDAGG_F32 ? 4 : 2;
+  const int half = kind == FEDAGG_F16    ? fedagg_host::kHalfF16
+                   : kind == FEDAGG_BF16 ? fedagg_host::kHalfBF16
+                                         : fedagg_host::kHalfNone;
   for (int i = 0; i < nseg && seg_bytes; ++i)
     if (seg_bytes[i] % esz) {
       fedagg_internal::set_error("fedagg_session_stage_check: segment not a whole number of elements");
@@ -508,13 +513,13 @@ int fedagg_session_stage_check(fedagg_session* s, void* d_dst, int K, int nseg, 
       fedagg_internal::set_error("fedagg_session_stage_check: byte range beyond the row");
       return FEDAGG_EINVAL;
     }
-    *mismatches = fedagg_host::check_rows(s->workers(), h_seg, seg_bytes, nseg, K, byte_lo, byte_hi - byte_lo, esz);
+    *mismatches = fedagg_host::check_rows(s->workers(), h_seg, seg_bytes, nseg, K, byte_lo, byte_hi - byte_lo, esz, half);
     return FEDAGG_OK;
   }
   uint64_t row = 0;
   int rc = stage_prepare(s, d_dst, byte_hi - byte_lo, K, nseg, h_seg, seg_bytes, byte_lo, byte_hi, &row);
   if (rc) return rc;
-  return stage_run(s, d_dst, row, K, nseg, h_seg, seg_bytes, byte_lo, row, esz, mismatches);
+  return stage_run(s, d_dst, row, K, nseg, h_seg, seg_bytes, byte_lo, row, esz, mismatches, half);
 }
 
 int fedagg_session_fetch(fedagg_session* s, const void* d_src, void* h_dst, uint64_t bytes) {

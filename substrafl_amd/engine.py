@@ -415,6 +415,36 @@ def bucket_dtype16(rows) -> Optional[np.dtype]:
     return None
 
 
+def scaffold_bucket_dtypes(pus, cvs, scv) -> Tuple[np.dtype, np.dtype, np.dtype, Optional[np.dtype]]:
+    """The kinds of a per-bucket Scaffold call (at least one bucket 16-bit), shared by
+    :meth:`AggregationEngine._scaffold_buckets` and the range-sharded route of
+    :mod:`multi_device`: ``(delta bucket, control-variate bucket, staged c, c as it arrived)``.  A
+    16-bit bucket keeps its dtype (staged raw); another bucket is f32 when all of its arrays are
+    (for the control-variate bucket, c too), else f64 through the exact cast.  c keeps its own
+    kind next to a 16-bit control-variate bucket (f64 when its arrays are not uniformly one of the
+    four kinds, the last element then None), else it takes the bucket's."""
+    f32, f64 = np.dtype(np.float32), np.dtype(np.float64)
+    c_dts = {a.dtype for row in scv for a in row}
+    c_dt = next(iter(c_dts)) if len(c_dts) == 1 else None
+    if c_dt is not None and not (c_dt == BF16 or c_dt in (np.float16, f32, f64)):
+        c_dt = None
+
+    def bucket_dtype(rows, with_c: bool) -> np.dtype:
+        dt = bucket_dtype16(rows)
+        if dt is not None:
+            return dt
+        AggregationEngine._float_rows(rows)
+        all32 = all(a.dtype == f32 for row in rows for a in row) and (not with_c or c_dt == f32)
+        return f32 if all32 else f64
+
+    dt_d, dt_c = bucket_dtype(pus, False), bucket_dtype(cvs, True)
+    # c: raw in its own kind next to a 16-bit control-variate bucket, else cast to the bucket's
+    dt_s = (c_dt if c_dt is not None else f64) if dt_c.itemsize == 2 else dt_c
+    if dt_s != c_dt:
+        AggregationEngine._float_rows(scv)
+    return dt_d, dt_c, dt_s, c_dt
+
+
 def c_mismatches16(c_rows) -> Tuple[int, str]:
     """Scaffold's server-control-variate check (scaffold.py:193-196) on the host for fp16 or
     ``wire.BF16`` copies: ``(mismatching elements of rows[1:] against rows[0], path)``.  Copies
@@ -1253,25 +1283,7 @@ class AggregationEngine:
         s = self.session()
         self.last_timing = tm = {}
         K, L = len(pus), len(pus[0])
-        f32, f64 = np.dtype(np.float32), np.dtype(np.float64)
-        c_dts = {a.dtype for row in scv for a in row}
-        c_dt = next(iter(c_dts)) if len(c_dts) == 1 else None
-        if c_dt is not None and not (c_dt == BF16 or c_dt in (np.float16, f32, f64)):
-            c_dt = None
-
-        def bucket_dtype(rows, with_c: bool) -> np.dtype:
-            dt = bucket_dtype16(rows)
-            if dt is not None:
-                return dt
-            self._float_rows(rows)
-            all32 = all(a.dtype == f32 for row in rows for a in row) and (not with_c or c_dt == f32)
-            return f32 if all32 else f64
-
-        dt_d, dt_c = bucket_dtype(pus, False), bucket_dtype(cvs, True)
-        # c: raw in its own kind next to a 16-bit control-variate bucket, else cast to the bucket's
-        dt_s = (c_dt if c_dt is not None else f64) if dt_c.itemsize == 2 else dt_c
-        if dt_s != c_dt:
-            self._float_rows(scv)
+        dt_d, dt_c, dt_s, c_dt = scaffold_bucket_dtypes(pus, cvs, scv)
         lid = list(range(L))
         lay_d = BucketLayout(lid, [a.shape for a in pus[0]], dt_d)
         lay_c = BucketLayout(lid, [a.shape for a in cvs[0]], dt_c)
@@ -1283,6 +1295,18 @@ class AggregationEngine:
         same_c = all(len(row) == len(scv[0]) and all(a is b for a, b in zip(row, scv[0])) for row in scv[1:])
         host_c = not same_c and c_dt is not None and (c_dt.itemsize == 2 or self.c_check == "host")
         Kc = 1 if (same_c or host_c) else K
+        if all(direct_rows(rows, dt, lay.M) is not None
+               for rows, dt, lay in ((pus, dt_d, lay_d), (cvs, dt_c, lay_c), (scv, dt_s, lay_s))):
+            # every bucket is stageable as it is: past the HBM budget the call streams through the
+            # GPU in parameter ranges, bucket by bucket (multi_device.scaffold_per_bucket)
+            ooc = self._out_of_core(K * (lay_d.ld * dt_d.itemsize + lay_c.ld * dt_c.itemsize)
+                                    + Kc * lay_s.ld * dt_s.itemsize + (lay_d.ld + lay_c.ld) * 8,
+                                    (self._B_BUCKET, self._B_CV, self._B_C, self._B_OUT, self._B_COUT, self._B_WS,
+                                     self._B_CNT))
+            if ooc is not None:
+                out = ooc.scaffold_per_bucket(pus, cvs, scv, n_samples, aggregation_lr, wire)
+                self.last_timing = {"out_of_core": ooc.last_timing}
+                return out
         d_d = s.buffer(self._B_BUCKET, K * lay_d.ld * dt_d.itemsize)
         d_cv = s.buffer(self._B_CV, K * lay_c.ld * dt_c.itemsize)
         d_cc = s.buffer(self._B_C, Kc * lay_s.ld * dt_s.itemsize)

@@ -175,7 +175,8 @@ def scaffold_average(strategy, shared_states, aggregation_lr, device: Optional[D
     check_same_shapes([*cvs, c0])  # np.sum([w*cv_k ..., c]) (scaffold.py:263)
     check_same_shapes(pus)  # np.sum([w*Δ_k ...]) (scaffold.py:293)
     engine = engine_for(device)
-    # kinds per bucket where the engine has them (16-bit buckets on one GPU), else one kind per call
+    # kinds per bucket where the engine has them (16-bit buckets, on one GPU or range-sharded over
+    # several), else one kind per call
     mismatches, new_c, avg = getattr(engine, "scaffold_per_bucket", engine.scaffold)(
         pus, cvs, _MirrorScaffold._server_control_variates(shared_states), [s.n_samples for s in shared_states],
         aggregation_lr, wire=wire)

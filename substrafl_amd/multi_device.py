@@ -34,11 +34,13 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native, runtime
-from .engine import (TILED_KINDS, AggregationEngine, FedAvgPlan, ScaffoldPlan, TiledFedAvgPlan, direct_rows,
-                     equal_count, fedavg_weights, kind_of, native_byte_order, reject_bf16, scaffold_weights,
-                     serialized, tiled_elems, tiled_recommended, tiled_tile)
+from .engine import (KIND_CODES, TILED_KINDS, AggregationEngine, FedAvgPlan, ScaffoldBucketPlan, ScaffoldPlan,
+                     TiledFedAvgPlan, bucket_dtype16, direct_rows, equal_count, fedavg_weights, kind_of,
+                     native_byte_order, reject_bf16, scaffold_bucket_dtypes, scaffold_weights, serialized, tiled_elems,
+                     tiled_recommended, tiled_tile)
 from .layout import ROW_ALIGN_BYTES, BucketLayout
 from .sharding import SHARD_ALIGN, shard_bounds
+from .wire import BF16
 
 HBM_HEADROOM = 0.85  # fraction of a device's free HBM one sub-range may use when no cap is given
 
@@ -426,6 +428,85 @@ class MultiDeviceEngine:
         new_c = [a for _, a in layout.unpack(out_c, wire)]
         return int(sum(mism)), new_c, avg
 
+    # ----------------------------------------------------------------------------------
+    def scaffold_per_bucket(self, parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                            aggregation_lr, wire: bool = False):
+        """:meth:`engine.AggregationEngine.scaffold_per_bucket` over the devices: what the strategies
+        call.  With no 16-bit bucket this is :meth:`scaffold`.  Otherwise the kinds are chosen per
+        bucket as on one GPU (``engine.scaffold_bucket_dtypes``) and, when every bucket's arrays
+        already have its kind, each bucket is sharded by parameter range: raw rows staged per
+        sub-range (2 B per element and client for a 16-bit bucket), the clients' ``c`` compared on
+        the pack workers while one copy is staged (any kind), one ``fedagg_scaffold_bucket`` launch
+        per sub-range, fp64 slices fetched into the one output.  Buckets that need a cast run on
+        the first device's engine.  Same return as :meth:`scaffold`."""
+        if (not parameters_updates or not parameters_updates[0] or (
+                bucket_dtype16(parameters_updates) is None and bucket_dtype16(control_variate_updates) is None)):
+            return self.scaffold(parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                                 aggregation_lr, wire)
+        return self._scaffold_buckets(parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                                      aggregation_lr, wire)
+
+    _BUCKET_SLOTS = (0, 1, 2, 5)
+
+    @serialized
+    def _scaffold_buckets(self, pus, cvs, scv, n_samples, aggregation_lr, wire: bool):
+        t_start = time.perf_counter()
+        pus, cvs, scv = (native_byte_order(x) for x in (pus, cvs, scv))
+        K, L = len(pus), len(pus[0])
+        dt_d, dt_c, dt_s, _ = scaffold_bucket_dtypes(pus, cvs, scv)
+        lid = list(range(L))
+        lay_d = BucketLayout(lid, [a.shape for a in pus[0]], dt_d)
+        lay_c = BucketLayout(lid, [a.shape for a in cvs[0]], dt_c)
+        lay_s = BucketLayout(lid, [a.shape for a in scv[0]], dt_s)
+        same_c = all(len(row) == len(scv[0]) and all(a is b for a, b in zip(row, scv[0])) for row in scv[1:])
+        rows_d = direct_rows(pus, dt_d, lay_d.M)
+        rows_c = direct_rows(cvs, dt_c, lay_c.M)
+        rows_s = direct_rows(scv[:1] if same_c else scv, dt_s, lay_s.M)
+        if rows_d is None or rows_c is None or rows_s is None or lay_s.M != lay_c.M:
+            return self._single().scaffold_per_bucket(pus, cvs, scv, n_samples, aggregation_lr, wire)  # casts
+        kd, kc, ks = kind_of(dt_d), kind_of(dt_c), kind_of(dt_s)
+        isz_d, isz_c, isz_s = dt_d.itemsize, dt_c.itemsize, dt_s.itemsize
+        w = scaffold_weights(n_samples)
+        lr = float(aggregation_lr)
+        pw_d, pw_c = lay_d.pairwise_idx.astype(np.int64), lay_c.pairwise_idx.astype(np.int64)
+        out_d = runtime.reusable_host_array(lay_d.M, np.float64, "multi-scaffold-delta")
+        out_c = runtime.reusable_host_array(lay_c.M, np.float64, "multi-scaffold-c")
+        # per element of a sub-range: K rows in, one fp64 out, and the one staged copy of c
+        ranges_d = self.plan_ranges(lay_d.M, K * isz_d + 8, self._BUCKET_SLOTS)
+        ranges_c = self.plan_ranges(lay_c.M, K * isz_c + 8 + isz_s, self._BUCKET_SLOTS)
+        ws_bytes = _native.load().fedagg_pairwise_ws_bytes(K, max(1, pw_d.size, pw_c.size), 8)
+        mism = [0] * len(self.devices)
+
+        def work(g, s):
+            for phase, rows, kind, isz, ranges, pw_all, out in ((0, rows_d, kd, isz_d, ranges_d, pw_d, out_d),
+                                                                (1, rows_c, kc, isz_c, ranges_c, pw_c, out_c)):
+                for lo, hi in ranges[g]:
+                    n = hi - lo
+                    ld = _ld(n, isz)
+                    d_rows = s.buffer(self._B_BUCKET, K * ld * isz)
+                    s.stage(d_rows, ld * isz, rows, byte_range=(lo * isz, hi * isz))
+                    d_cc = None
+                    if phase == 1:
+                        ld_s = _ld(n, isz_s)
+                        d_cc = s.buffer(self._B_C, ld_s * isz_s)
+                        if same_c:
+                            s.stage(d_cc, ld_s * isz_s, rows_s, byte_range=(lo * isz_s, hi * isz_s))
+                        else:
+                            mism[g] += s.stage_check(d_cc, rows_s, dt_s, byte_range=(lo * isz_s, hi * isz_s))
+                    d_out = s.buffer(self._B_OUT, _ld(n, 8) * 8)
+                    ws = s.buffer(self._B_WS, ws_bytes)
+                    pw = (pw_all[(pw_all >= lo) & (pw_all < hi)] - lo).astype(np.uint64)
+                    ScaffoldBucketPlan(kind, [d_rows + k * ld * isz for k in range(K)], phase, d_cc,
+                                       ks if phase == 1 else None, w, n, lr, d_out, pw, ws).launch(s.stream)
+                    s.fetch(d_out, out[lo:hi])
+
+        self._run(work)
+        self.last_timing = {"total_s": time.perf_counter() - t_start, "ranges": ranges_d, "ranges_cv": ranges_c,
+                            "bucket_kinds": (kd, kc, ks), "c_check": "identity" if same_c else "host"}
+        avg = [a for _, a in lay_d.unpack(out_d, wire)]
+        new_c = [a for _, a in lay_c.unpack(out_c, wire)]
+        return int(sum(mism)), new_c, avg
+
 
 class NativeMultiFedAvg:
     """The one-call C entry ``fedagg_multi_*`` (csrc/multi.hip) from Python: the same
@@ -491,3 +572,65 @@ class NativeMultiFedAvg:
             _native.check(self.lib.fedagg_multi_shard_info(self._h, g, *[ctypes.byref(x) for x in v]), "shard_info")
             out.append(dict(zip(("device", "numa_node", "threads", "cpus", "lo", "hi", "ranges"), [x.value for x in v])))
         return out
+
+
+class NativeMultiScaffold(NativeMultiFedAvg):
+    """Scaffold on the one-call C entry (``fedagg_multi_scaffold_bucket``, csrc/multi.hip): one
+    aggregation is two ctypes calls, the delta bucket then the control-variate bucket, each
+    sharded by parameter range over ``devices`` entirely in C++ (what a host in another language
+    binds).  Each bucket's arrays are uniformly fp16, ``wire.BF16``, fp32 or
+    fp64 and are staged as they are; ``c`` may be any of the four next to a 16-bit
+    control-variate bucket and has the bucket's kind next to an fp32 / fp64 one.  Bit-identical to
+    ``fedagg_scaffold_bucket`` over the whole range and to the reference (scaffold.py:193-196,
+    262-263, 293)."""
+
+    @staticmethod
+    def _uniform(rows, what: str) -> np.dtype:
+        dts = {np.asarray(a).dtype for row in rows for a in row}
+        dt = next(iter(dts)) if len(dts) == 1 else None
+        if dt is None or not (dt == BF16 or dt in (np.float16, np.float32, np.float64)):
+            raise NotImplementedError(f"fedagg_multi_scaffold_bucket takes {what} of one dtype: float16, wire.BF16, "
+                                      "float32 or float64")
+        return np.dtype(dt)
+
+    def scaffold(self, parameters_updates, control_variate_updates, server_control_variates, n_samples,
+                 aggregation_lr):
+        """scaffold.py:193-196 (the equality of the clients' ``c``, as a mismatch count) and
+        :297-337 for validated inputs.  Returns ``(mismatches, new_server_control_variate,
+        avg_parameters_update)``, both fp64."""
+        import ctypes
+
+        pus, cvs, scv = (native_byte_order(x) for x in (parameters_updates, control_variate_updates,
+                                                        server_control_variates))
+        K, L = len(pus), len(pus[0])
+        dt_d, dt_c, dt_s = (self._uniform(pus, "parameter updates"), self._uniform(cvs, "control-variate updates"),
+                            self._uniform(scv, "server control variates"))
+        if dt_c.itemsize != 2 and dt_s != dt_c:
+            raise NotImplementedError("fedagg_multi_scaffold_bucket: next to a float32 / float64 control-variate "
+                                      "bucket the server control variate has the bucket's dtype")
+        lid = list(range(L))
+        lay_d = BucketLayout(lid, [a.shape for a in pus[0]], dt_d)
+        lay_c = BucketLayout(lid, [a.shape for a in cvs[0]], dt_c)
+        same_c = all(len(row) == len(scv[0]) and all(a is b for a, b in zip(row, scv[0])) for row in scv[1:])
+        Kc = 1 if same_c else K
+        w = scaffold_weights(n_samples)
+        out_d = runtime.reusable_host_array(lay_d.M, np.float64, "multi-native-scaffold-delta")
+        out_c = runtime.reusable_host_array(lay_c.M, np.float64, "multi-native-scaffold-c")
+        fn = self.lib.fedagg_multi_scaffold_bucket
+        nseg, ptrs, sizes, keep = runtime._segments(pus)
+        idx = lay_d.pairwise_idx.astype(np.uint64)
+        _native.check(fn(self._h, 0, K, nseg, ptrs, sizes, KIND_CODES[kind_of(dt_d)], w.ctypes.data,
+                         float(aggregation_lr), 0, 0, None, None, 0, idx.ctypes.data if idx.size else None,
+                         int(idx.size), out_d.ctypes.data, None), "fedagg_multi_scaffold_bucket (delta)")
+        nseg, ptrs, sizes, keep = runtime._segments(cvs)
+        c_nseg, c_ptrs, c_sizes, c_keep = runtime._segments(scv[:Kc])
+        idx = lay_c.pairwise_idx.astype(np.uint64)
+        mism = ctypes.c_uint64(0)
+        _native.check(fn(self._h, 1, K, nseg, ptrs, sizes, KIND_CODES[kind_of(dt_c)], w.ctypes.data,
+                         float(aggregation_lr), Kc, c_nseg, c_ptrs, c_sizes, KIND_CODES[kind_of(dt_s)],
+                         idx.ctypes.data if idx.size else None, int(idx.size), out_c.ctypes.data,
+                         ctypes.byref(mism)), "fedagg_multi_scaffold_bucket (control variate)")
+        del keep, c_keep
+        avg = [a for _, a in lay_d.unpack(out_d)]
+        new_c = [a for _, a in lay_c.unpack(out_c)]
+        return int(mism.value), new_c, avg

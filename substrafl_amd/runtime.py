@@ -176,8 +176,13 @@ class Session:
         """Stage ``rows[0]`` (bytes ``byte_range`` of it, default all) to ``d_dst`` and compare the
         same bytes of every other row with it by value on the host
         (``fedagg_session_stage_check``: Scaffold's server-control-variate check,
-        scaffold.py:193-196).  Returns the number of mismatching elements."""
-        kind = {np.dtype(np.float32): _native.FEDAGG_F32, np.dtype(np.float64): _native.FEDAGG_F64}[np.dtype(dtype)]
+        scaffold.py:193-196).  ``dtype``: float16, ``wire.BF16``, float32 or float64.  Returns the
+        number of mismatching elements."""
+        from .wire import BF16
+
+        dtype = np.dtype(dtype)
+        kind = {np.dtype(np.float16): _native.FEDAGG_F16, BF16: _native.FEDAGG_BF16,
+                np.dtype(np.float32): _native.FEDAGG_F32, np.dtype(np.float64): _native.FEDAGG_F64}[dtype]
         nseg, ptrs, sizes, keep = _segments(rows)
         for row in rows:
             for a in row:
