@@ -657,6 +657,20 @@ int fedagg_multi_fedavg_f64(fedagg_multi* m, int K, int nseg, const void* const*
 /* fp16 buckets: h_w and h_out hold fp16 bit patterns (fedagg_fedavg_f16's semantics, NumPy's half loops) */
 int fedagg_multi_fedavg_f16(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
                             const uint16_t* h_w, const uint64_t* h_idx, int P, uint16_t* h_out);
+/* bf16 buckets (added within ABI 17): rows of bf16 bit patterns, h_w the K fp32 weights fl(n_k / n),
+ * h_out M floats.  Replaces fed_avg.py:217-222 on the exact fp32 upcast of the rows, as
+ * fedagg_fedavg_bf16 (fp32 product, accumulator and output; the reference itself cannot carry bf16).
+ * Every sub-range is one fedagg_fedavg_bf16 launch over the elements it owns, so h_out is
+ * bit-identical to one whole-range fedagg_fedavg_bf16.  Each element of a sub-range takes K * 2 + 4
+ * bytes of HBM.  Without "max_shard_bytes" the budget of a sub-range is that of
+ * fedagg_multi_scaffold_bucket below: 85 % of the device's free HBM, read once per device before
+ * the shard threads start, divided by the shards on that device, less the numel == 1 workspace (the
+ * three entries above keep their own plan: every shard thread reads its device's free HBM itself).
+ * M == 0: FEDAGG_OK, nothing touched.  Bad arguments return FEDAGG_EINVAL before any HIP call, each
+ * with its own text, checked in this order: K <= 0; NULL h_w, nseg < 0, NULL tables with nseg > 0,
+ * P < 0, NULL h_idx with P > 0; a segment of an odd byte count; an index >= M; NULL h_out; NULL m. */
+int fedagg_multi_fedavg_bf16(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
+                             const float* h_w, const uint64_t* h_idx, int P, float* h_out);
 /* Scaffold on the same plan: ONE bucket per call, as fedagg_scaffold_bucket, over host rows -- an
  * aggregation is two calls.  Replaces scaffold.py:293 (phase 0, the delta bucket: lr * sum_k w_k *
  * delta_k), scaffold.py:262-263 (phase 1, the control-variate bucket: sum_k w_k * cv_k, then + c

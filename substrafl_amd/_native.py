@@ -157,6 +157,7 @@ SIGNATURES = {
     "fedagg_multi_fedavg_f32": (c_int, [c_void, c_int, c_int, P(c_void), P(c_u64), c_void, c_void, c_int, c_void]),
     "fedagg_multi_fedavg_f64": (c_int, [c_void, c_int, c_int, P(c_void), P(c_u64), c_void, c_void, c_int, c_void]),
     "fedagg_multi_fedavg_f16": (c_int, [c_void, c_int, c_int, P(c_void), P(c_u64), c_void, c_void, c_int, c_void]),
+    "fedagg_multi_fedavg_bf16": (c_int, [c_void, c_int, c_int, P(c_void), P(c_u64), c_void, c_void, c_int, c_void]),
     "fedagg_multi_scaffold_bucket": (c_int, [c_void, c_int, c_int, c_int, P(c_void), P(c_u64), c_int, c_void, c_dbl,
                                              c_int, c_int, P(c_void), P(c_u64), c_int, c_void, c_int, c_void,
                                              P(c_u64)]),

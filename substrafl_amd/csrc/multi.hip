@@ -16,7 +16,8 @@
 //     numel == 1 patch of the elements it owns, fetch its slice straight into the caller's output.
 // Every output element is computed by the single-GPU kernel's arithmetic, so the result is bit-
 // identical to fedagg_fedavg_* over the whole range and to the reference (fed_avg.py:217-222): no
-// collective, no re-association.
+// collective, no re-association.  bf16 rows (fedagg_multi_fedavg_bf16) run the same plan with
+// 2-byte elements in and fp32 out: K * 2 + 4 bytes of HBM per element of a sub-range.
 //
 // Scaffold runs on the same plan one bucket per call (fedagg_multi_scaffold_bucket): rows of any
 // float kind staged as they are, fedagg_scaffold_bucket per sub-range, and the clients' copies of c
@@ -157,17 +158,18 @@ int shard_budget(fedagg_multi* m, Shard& sh, uint64_t* budget) {
   return FEDAGG_OK;
 }
 
-template <class T>
+// The bucket kernel of rows of In averaged into Out (In == Out but for bf16 rows, fp32 output).
+template <class In, class Out>
 struct KernelOf;
 template <>
-struct KernelOf<float> {
+struct KernelOf<float, float> {
   static int run(const float* const* rows, const void* w, int K, uint64_t n, const uint64_t* idx, int P, void* ws,
                  void* out, void* stream) {
     return fedagg_fedavg_f32(rows, static_cast<const float*>(w), K, n, idx, P, ws, static_cast<float*>(out), stream);
   }
 };
 template <>
-struct KernelOf<double> {
+struct KernelOf<double, double> {
   static int run(const double* const* rows, const void* w, int K, uint64_t n, const uint64_t* idx, int P, void* ws,
                  void* out, void* stream) {
     return fedagg_fedavg_f64(rows, static_cast<const double*>(w), K, n, idx, P, ws, static_cast<double*>(out),
@@ -176,7 +178,7 @@ struct KernelOf<double> {
 };
 
 template <>
-struct KernelOf<uint16_t> {  // fp16 buckets (bit patterns), fp16 weights and output: NumPy's half loops
+struct KernelOf<uint16_t, uint16_t> {  // fp16 buckets (bit patterns), fp16 weights and output: NumPy's half loops
   static int run(const uint16_t* const* rows, const void* w, int K, uint64_t n, const uint64_t* idx, int P, void* ws,
                  void* out, void* stream) {
     return fedagg_fedavg_f16(rows, static_cast<const uint16_t*>(w), K, n, idx, P, ws, static_cast<uint16_t*>(out),
@@ -184,21 +186,71 @@ struct KernelOf<uint16_t> {  // fp16 buckets (bit patterns), fp16 weights and ou
   }
 };
 
-// One shard: its sub-ranges through its GPU, in order.
-template <class T>
+template <>
+struct KernelOf<uint16_t, float> {  // bf16 buckets (bit patterns), fp32 weights, product, accumulator and output
+  static int run(const uint16_t* const* rows, const void* w, int K, uint64_t n, const uint64_t* idx, int P, void* ws,
+                 void* out, void* stream) {
+    return fedagg_fedavg_bf16(rows, static_cast<const float*>(w), K, n, idx, P, ws, static_cast<float*>(out), stream);
+  }
+};
+
+// shard_bounds(M, G): equal, 512-element-multiple chunks; the last shards may get less or nothing
+void set_shard_bounds(fedagg_multi* m, uint64_t M) {
+  const uint64_t G = m->shards.size();
+  uint64_t chunk = (M + G - 1) / G;
+  chunk = (chunk + kShardAlign - 1) / kShardAlign * kShardAlign;
+  for (uint64_t gi = 0; gi < G; ++gi) {
+    m->shards[gi].lo = std::min(M, gi * chunk);
+    m->shards[gi].hi = std::min(M, (gi + 1) * chunk);
+    m->shards[gi].ranges = 0;
+  }
+}
+
+// HBM one sub-range of every shard may take, per device.  The shard threads of one device all
+// allocate from the same free HBM, so it is read once per distinct device here, before any of them
+// starts, and divided by the shards on that device; the numel == 1 workspace comes off before the
+// step is computed.  With "max_shard_bytes" set that is every shard's budget.
+int device_budgets(fedagg_multi* m, size_t ws_bytes, const std::string& name, std::vector<uint64_t>* budget) {
+  const uint64_t G = m->shards.size();
+  budget->assign(G, m->max_shard_bytes);
+  if (m->max_shard_bytes) return FEDAGG_OK;
+  for (uint64_t gi = 0; gi < G; ++gi) {
+    if ((*budget)[gi]) continue;  // filled in with an earlier shard of the same device
+    const int dev = m->shards[gi].device;
+    uint64_t free_b = 0, total_b = 0, held = 0, n_on_dev = 0;
+    const int rc = fedagg_device_memory(dev, &free_b, &total_b);
+    if (rc) {
+      const std::string e = fedagg_last_error();
+      fail(name + ": free HBM of device " + std::to_string(dev) + ": " + e);
+      return rc;
+    }
+    for (const Shard& sh : m->shards)
+      if (sh.device == dev) {
+        ++n_on_dev;
+        for (uint64_t h : sh.held) held += h;
+      }
+    const uint64_t share = (uint64_t)((double)(free_b + held) * kHeadroom) / n_on_dev;
+    for (uint64_t gj = gi; gj < G; ++gj)
+      if (m->shards[gj].device == dev) (*budget)[gj] = std::max<uint64_t>(1, share - std::min<uint64_t>(share, ws_bytes));
+  }
+  return FEDAGG_OK;
+}
+
+// One shard: its sub-ranges through its GPU, in order.  Rows of In, a result of Out; `budget` is the
+// HBM one sub-range may take (0: the shard's own free HBM, read here).
+template <class In, class Out>
 int run_shard(fedagg_multi* m, Shard& sh, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
-              const void* h_w, const std::vector<uint64_t>& idx, T* h_out, size_t ws_bytes) {
-  const uint64_t esz = sizeof(T);
+              const void* h_w, const std::vector<uint64_t>& idx, Out* h_out, size_t ws_bytes, uint64_t budget) {
+  const uint64_t esz = sizeof(In), osz = sizeof(Out);
   sh.ranges = 0;
   sh.stage_s = sh.kernel_fetch_s = 0;
   if (sh.hi <= sh.lo) return FEDAGG_OK;
   int rc = fedagg_session_activate(sh.s);
   if (rc) return rc;
-  uint64_t budget = 0;
-  if ((rc = shard_budget(m, sh, &budget))) return rc;
-  uint64_t cap = std::max<uint64_t>(kShardAlign, budget / ((uint64_t)(K + 1) * esz));
+  if (!budget && (rc = shard_budget(m, sh, &budget))) return rc;
+  uint64_t cap = std::max<uint64_t>(kShardAlign, budget / ((uint64_t)K * esz + osz));
   const uint64_t step = std::max(kShardAlign, cap / kShardAlign * kShardAlign);  // multi_device._split
-  std::vector<const T*> rows(K);
+  std::vector<const In*> rows(K);
   std::vector<uint64_t> pw;
   for (uint64_t lo = sh.lo; lo < sh.hi; lo += step) {
     const uint64_t hi = std::min(sh.hi, lo + step), n = hi - lo, ld = row_ld(n, esz);
@@ -208,21 +260,67 @@ int run_shard(fedagg_multi* m, Shard& sh, int K, int nseg, const void* const* h_
     if ((rc = fedagg_session_stage_range(sh.s, d_bucket, ld * esz, K, nseg, h_seg, seg_bytes, lo * esz, hi * esz)))
       return rc;
     const double t1 = now_s();
-    if ((rc = shard_buffer(sh, kSlotOut, ld * esz, &d_out))) return rc;
+    if ((rc = shard_buffer(sh, kSlotOut, row_ld(n, osz) * osz, &d_out))) return rc;
     if ((rc = shard_buffer(sh, kSlotWs, ws_bytes, &d_ws))) return rc;
     pw.clear();
     for (uint64_t i : idx)
       if (i >= lo && i < hi) pw.push_back(i - lo);
     for (int k = 0; k < K; ++k)
-      rows[k] = reinterpret_cast<const T*>(static_cast<const char*>(d_bucket) + (uint64_t)k * ld * esz);
-    if ((rc = KernelOf<T>::run(rows.data(), h_w, K, n, pw.empty() ? nullptr : pw.data(), (int)pw.size(), d_ws, d_out,
-                               fedagg_session_stream(sh.s))))
+      rows[k] = reinterpret_cast<const In*>(static_cast<const char*>(d_bucket) + (uint64_t)k * ld * esz);
+    if ((rc = KernelOf<In, Out>::run(rows.data(), h_w, K, n, pw.empty() ? nullptr : pw.data(), (int)pw.size(), d_ws,
+                                     d_out, fedagg_session_stream(sh.s))))
       return rc;
-    if ((rc = fedagg_session_fetch(sh.s, d_out, h_out + lo, n * esz))) return rc;
+    if ((rc = fedagg_session_fetch(sh.s, d_out, h_out + lo, n * osz))) return rc;
     sh.stage_s += t1 - t0;
     sh.kernel_fetch_s += now_s() - t1;
     ++sh.ranges;
   }
+  return FEDAGG_OK;
+}
+
+// The checked call: M > 0 elements of In per row over the shards, into M elements of Out.
+// `per_device`: the budget rule of device_budgets (else every shard thread reads its own free HBM).
+template <class In, class Out>
+int run_fedavg(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes, const void* h_w,
+               const std::vector<uint64_t>& idx, uint64_t M, Out* h_out, const std::string& name, bool per_device) {
+  std::lock_guard<std::mutex> g(m->m);
+  int caller = -1;
+  (void)hipGetDevice(&caller);
+  const uint64_t G = m->shards.size();
+  set_shard_bounds(m, M);
+  const size_t ws_bytes = fedagg_pairwise_ws_bytes(K, std::max(1, (int)idx.size()), 8);
+  std::vector<uint64_t> budget(G, 0);
+  if (per_device)
+    if (const int rc = device_budgets(m, ws_bytes, name, &budget)) {
+      if (caller >= 0) (void)hipSetDevice(caller);
+      return rc;
+    }
+  std::vector<int> rcs(G, FEDAGG_OK);
+  std::vector<std::string> errs(G);
+  std::vector<std::thread> th;
+  bool spawned = true;
+  try {
+    for (uint64_t gi = 0; gi < G; ++gi)
+      th.emplace_back([&, gi] {
+        rcs[gi] = run_shard<In, Out>(m, m->shards[gi], K, nseg, h_seg, seg_bytes, h_w, idx, h_out, ws_bytes,
+                                     budget[gi]);
+        if (rcs[gi]) errs[gi] = fedagg_last_error();  // the error text is per thread: carry it back
+      });
+  } catch (const std::exception& e) {  // no thread for a shard: the started ones finish, the call fails
+    spawned = false;
+    errs.assign(G, std::string("cannot start a shard thread: ") + e.what());
+  }
+  for (auto& t : th) t.join();
+  if (caller >= 0) (void)hipSetDevice(caller);  // the caller's later work stays on its own device
+  if (!spawned) return fail(name + ": " + errs[0]);
+  for (uint64_t gi = 0; gi < G; ++gi)
+    if (rcs[gi]) {
+      char buf[640];
+      snprintf(buf, sizeof(buf), "%s: shard %d (device %d): %s", name.c_str(), (int)gi, m->shards[gi].device,
+               errs[gi].c_str());
+      fedagg_internal::set_error(buf);
+      return rcs[gi];
+    }
   return FEDAGG_OK;
 }
 
@@ -242,46 +340,7 @@ int multi_fedavg(fedagg_multi* m, int K, int nseg, const void* const* h_seg, con
   for (uint64_t i : idx)
     if (i >= M) return fail(std::string(name) + ": numel == 1 index out of range");
   if (M == 0) return FEDAGG_OK;
-  std::lock_guard<std::mutex> g(m->m);
-  int caller = -1;
-  (void)hipGetDevice(&caller);
-  // shard_bounds(M, G): equal, 512-element-multiple chunks; the last shards may get less or nothing
-  const uint64_t G = m->shards.size();
-  uint64_t chunk = (M + G - 1) / G;
-  chunk = (chunk + kShardAlign - 1) / kShardAlign * kShardAlign;
-  for (uint64_t gi = 0; gi < G; ++gi) {
-    m->shards[gi].lo = std::min(M, gi * chunk);
-    m->shards[gi].hi = std::min(M, (gi + 1) * chunk);
-  }
-  const size_t ws_bytes = fedagg_pairwise_ws_bytes(K, std::max(1, P), 8);
-  std::vector<int> rcs(G, FEDAGG_OK);
-  std::vector<std::string> errs(G);
-  std::vector<std::thread> th;
-  int spawn_rc = FEDAGG_OK;
-  try {
-    for (uint64_t gi = 0; gi < G; ++gi)
-      th.emplace_back([&, gi] {
-        rcs[gi] = run_shard<T>(m, m->shards[gi], K, nseg, h_seg, seg_bytes, h_w, idx, h_out, ws_bytes);
-        if (rcs[gi]) errs[gi] = fedagg_last_error();  // the error text is per thread: carry it back
-      });
-  } catch (const std::exception& e) {  // no thread for a shard: the started ones finish, the call fails
-    spawn_rc = FEDAGG_EINVAL;
-    errs.assign(G, std::string("cannot start a shard thread: ") + e.what());
-  }
-  for (auto& t : th) t.join();
-  if (spawn_rc) {
-    if (caller >= 0) (void)hipSetDevice(caller);
-    return fail(std::string(name) + ": " + errs[0]);
-  }
-  if (caller >= 0) (void)hipSetDevice(caller);  // the caller's later work stays on its own device
-  for (uint64_t gi = 0; gi < G; ++gi)
-    if (rcs[gi]) {
-      char buf[640];
-      snprintf(buf, sizeof(buf), "%s: shard %d (device %d): %s", name, (int)gi, m->shards[gi].device, errs[gi].c_str());
-      fedagg_internal::set_error(buf);
-      return rcs[gi];
-    }
-  return FEDAGG_OK;
+  return run_fedavg<T, T>(m, K, nseg, h_seg, seg_bytes, h_w, idx, M, h_out, name, false);
 }
 
 // ---- Scaffold, one bucket per call (fedagg_multi_scaffold_bucket) ----------------------------
@@ -463,6 +522,28 @@ int fedagg_multi_fedavg_f16(fedagg_multi* m, int K, int nseg, const void* const*
   return multi_fedavg<uint16_t>(m, K, nseg, h_seg, seg_bytes, h_w, h_idx, P, h_out, "fedagg_multi_fedavg_f16");
 }
 
+int fedagg_multi_fedavg_bf16(fedagg_multi* m, int K, int nseg, const void* const* h_seg, const uint64_t* seg_bytes,
+                             const float* h_w, const uint64_t* h_idx, int P, float* h_out) {
+  const std::string name = "fedagg_multi_fedavg_bf16";
+  // every argument check comes before the first HIP call, the engine last
+  if (K <= 0) return fail(name + ": K must be > 0");
+  if (!h_w || nseg < 0 || (nseg > 0 && (!h_seg || !seg_bytes)) || P < 0 || (P > 0 && !h_idx))
+    return fail(name + ": invalid argument");
+  uint64_t row = 0;
+  for (int i = 0; i < nseg; ++i) {
+    if (seg_bytes[i] % 2) return fail(name + ": segment not a whole number of elements");
+    row += seg_bytes[i];
+  }
+  const uint64_t M = row / 2;
+  std::vector<uint64_t> idx(h_idx, h_idx + P);
+  for (uint64_t i : idx)
+    if (i >= M) return fail(name + ": numel == 1 index out of range");
+  if (!h_out) return fail(name + ": NULL h_out");
+  if (!m) return fail(name + ": NULL engine");
+  if (M == 0) return FEDAGG_OK;
+  return run_fedavg<uint16_t, float>(m, K, nseg, h_seg, seg_bytes, h_w, idx, M, h_out, name, true);
+}
+
 int fedagg_multi_scaffold_bucket(fedagg_multi* m, int phase, int K, int nseg, const void* const* h_rows,
                                  const uint64_t* seg_bytes, int row_kind, const double* h_w, double lr, int Kc,
                                  int c_nseg, const void* const* h_c, const uint64_t* c_seg_bytes, int c_kind,
@@ -516,38 +597,11 @@ int fedagg_multi_scaffold_bucket(fedagg_multi* m, int phase, int K, int nseg, co
   int caller = -1;
   (void)hipGetDevice(&caller);
   const uint64_t G = m->shards.size();
-  uint64_t chunk = (M + G - 1) / G;  // shard_bounds(M, G), as multi_fedavg
-  chunk = (chunk + kShardAlign - 1) / kShardAlign * kShardAlign;
-  for (uint64_t gi = 0; gi < G; ++gi) {
-    m->shards[gi].lo = std::min(M, gi * chunk);
-    m->shards[gi].hi = std::min(M, (gi + 1) * chunk);
-    m->shards[gi].ranges = 0;
-  }
-  // HBM one sub-range may take.  The shard threads of one device all allocate from the same free
-  // HBM, so it is read once per distinct device here, before any of them starts, and divided by
-  // the shards on that device; the numel == 1 workspace comes off before the step is computed.
-  std::vector<uint64_t> budget(G, m->max_shard_bytes);
-  if (!m->max_shard_bytes) {
-    for (uint64_t gi = 0; gi < G; ++gi) {
-      if (budget[gi]) continue;  // filled in with an earlier shard of the same device
-      const int dev = m->shards[gi].device;
-      uint64_t free_b = 0, total_b = 0, held = 0, n_on_dev = 0;
-      const int rc = fedagg_device_memory(dev, &free_b, &total_b);
-      if (rc) {
-        const std::string e = fedagg_last_error();
-        if (caller >= 0) (void)hipSetDevice(caller);
-        fail(name + ": free HBM of device " + std::to_string(dev) + ": " + e);
-        return rc;
-      }
-      for (const Shard& sh : m->shards)
-        if (sh.device == dev) {
-          ++n_on_dev;
-          for (uint64_t h : sh.held) held += h;
-        }
-      const uint64_t share = (uint64_t)((double)(free_b + held) * kHeadroom) / n_on_dev;
-      for (uint64_t gj = gi; gj < G; ++gj)
-        if (m->shards[gj].device == dev) budget[gj] = std::max<uint64_t>(1, share - std::min<uint64_t>(share, a.ws_bytes));
-    }
+  set_shard_bounds(m, M);
+  std::vector<uint64_t> budget;
+  if (const int rc = device_budgets(m, a.ws_bytes, name, &budget)) {
+    if (caller >= 0) (void)hipSetDevice(caller);
+    return rc;
   }
   std::vector<int> rcs(G, FEDAGG_OK);
   std::vector<uint64_t> bad(G, 0);

@@ -286,7 +286,6 @@ class MultiDeviceEngine:
         """fed_avg.py:217-222 for validated inputs, sharded by parameter range over the devices."""
         t_start = time.perf_counter()
         parameters_updates = native_byte_order(parameters_updates)
-        K = len(parameters_updates)
         L = len(parameters_updates[0])
         if L == 0:
             return []
@@ -295,14 +294,20 @@ class MultiDeviceEngine:
         R = np.result_type(next(iter(dts)), 1.0) if len(dts) == 1 else None
         if R is None or R != next(iter(dts)) or R not in (np.float16, np.float32, np.float64):
             return self._single().fedavg(parameters_updates, n_samples, wire)  # dtype groups / casts
+        return self._fedavg_ranges(parameters_updates, n_samples, wire, R, R, t_start)
+
+    def _fedavg_ranges(self, parameters_updates, n_samples, wire: bool, R: np.dtype, Rout: np.dtype, t_start: float):
+        """The sharded plan over rows uniformly of dtype ``R`` averaged into ``Rout`` (``R`` itself,
+        or float32 for ``wire.BF16`` rows): per sub-range ``K`` rows of ``R`` in, one of ``Rout`` out."""
+        K, L = len(parameters_updates), len(parameters_updates[0])
         layout = BucketLayout(list(range(L)), [a.shape for a in parameters_updates[0]], R)
-        M, isz = layout.M, R.itemsize
+        M, isz, osz = layout.M, R.itemsize, Rout.itemsize
         rows = direct_rows(parameters_updates, R, M)
         kind = kind_of(R)
         w = fedavg_weights(n_samples, kind)
         pw_all = layout.pairwise_idx.astype(np.int64)
-        out = runtime.reusable_host_array(M, R, "multi-fedavg")
-        ranges = self.plan_ranges(M, (K + 1) * isz, self._FEDAVG_SLOTS)
+        out = runtime.reusable_host_array(M, Rout, "multi-fedavg")
+        ranges = self.plan_ranges(M, K * isz + osz, self._FEDAVG_SLOTS)
         ws_bytes = _native.load().fedagg_pairwise_ws_bytes(K, max(1, pw_all.size), 8)
         timing: List[Dict[str, float]] = [dict() for _ in self.devices]
 
@@ -322,7 +327,7 @@ class MultiDeviceEngine:
                     d_bucket = s.buffer(self._B_BUCKET, K * ld * isz)
                     s.stage(d_bucket, ld * isz, rows, byte_range=(lo * isz, hi * isz))
                 t1 = time.perf_counter()
-                d_out = s.buffer(self._B_OUT, ld * isz)
+                d_out = s.buffer(self._B_OUT, _ld(n, osz) * osz)
                 ws = s.buffer(self._B_WS, ws_bytes)
                 pw = (pw_all[(pw_all >= lo) & (pw_all < hi)] - lo).astype(np.uint64)
                 if self.kernel_events:
@@ -348,6 +353,23 @@ class MultiDeviceEngine:
         for li, arr in layout.unpack(out, wire):
             results[li] = arr
         return results  # type: ignore[return-value]
+
+    def fedavg_routed(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
+                      wire: bool = False) -> List[np.ndarray]:
+        """What the strategies call: :meth:`fedavg`, and for updates that are uniformly
+        ``wire.BF16`` the same sharded plan over 2-byte rows with an fp32 result (each sub-range one
+        ``fedagg_fedavg_bf16`` / ``_tiled_bf16`` launch, ``K * 2 + 4`` bytes of HBM per element), bit-
+        identical to :class:`engine.AggregationEngine` on one GPU.  :meth:`fedavg` itself keeps
+        refusing ``wire.BF16`` (its refusal is pinned by tests), so the route is this name."""
+        if (not parameters_updates or not parameters_updates[0]
+                or not all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
+            return self.fedavg(parameters_updates, n_samples, wire)
+        return self._fedavg_bf16(parameters_updates, n_samples, wire)
+
+    @serialized
+    def _fedavg_bf16(self, parameters_updates, n_samples, wire: bool):
+        return self._fedavg_ranges(native_byte_order(parameters_updates), n_samples, wire, BF16,
+                                   np.dtype(np.float32), time.perf_counter())
 
     # ----------------------------------------------------------------------------------
     @serialized
@@ -513,8 +535,9 @@ class NativeMultiFedAvg:
     parameter-range plan as :class:`MultiDeviceEngine` -- shards, one thread and one private session
     per device, NUMA-bound pack workers, HBM-sized sub-ranges -- run entirely in C++, one ctypes call
     per aggregation (what a host in another language binds).  FedAvg over
-    uniform fp16, fp32 or fp64 layer lists; bit-identical to :class:`MultiDeviceEngine` and to the
-    reference (fed_avg.py:217-222)."""
+    uniform fp16, fp32 or fp64 layer lists (:meth:`fedavg`) or ``wire.BF16`` ones
+    (:meth:`fedavg_bf16`); bit-identical to :class:`MultiDeviceEngine` and to the reference
+    (fed_avg.py:217-222)."""
 
     def __init__(self, devices: Sequence[int], pack_threads: int = 0, max_shard_bytes: int = 0):
         import ctypes
@@ -558,6 +581,23 @@ class NativeMultiFedAvg:
         fn = getattr(self.lib, f"fedagg_multi_fedavg_{kind}")
         _native.check(fn(self._h, K, nseg, ptrs, sizes, w.ctypes.data, idx.ctypes.data if idx.size else None,
                          int(idx.size), out.ctypes.data), "fedagg_multi_fedavg")
+        del keep
+        return [a for _, a in layout.unpack(out)]
+
+    def fedavg_bf16(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int]) -> List[np.ndarray]:
+        """fed_avg.py:217-222 on the exact fp32 upcast of validated inputs whose layers are all
+        ``wire.BF16`` (``fedagg_multi_fedavg_bf16``): fp32 weights, fp32 layers back."""
+        K, L = len(parameters_updates), len(parameters_updates[0])
+        if not all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu):
+            raise NotImplementedError("fedagg_multi_fedavg_bf16 takes layers that are all wire.BF16")
+        layout = BucketLayout(list(range(L)), [a.shape for a in parameters_updates[0]], BF16)
+        nseg, ptrs, sizes, keep = runtime._segments(native_byte_order(parameters_updates))
+        w = fedavg_weights(n_samples, "bf16")
+        idx = layout.pairwise_idx.astype(np.uint64)
+        out = runtime.reusable_host_array(layout.M, np.float32, "multi-native")
+        _native.check(self.lib.fedagg_multi_fedavg_bf16(self._h, K, nseg, ptrs, sizes, w.ctypes.data,
+                                                        idx.ctypes.data if idx.size else None, int(idx.size),
+                                                        out.ctypes.data), "fedagg_multi_fedavg_bf16")
         del keep
         return [a for _, a in layout.unpack(out)]
 

@@ -87,5 +87,7 @@ def weighted_average(shared_states, state_name: str, device: Devices = None, wir
     updates = [list(state.parameters_update) for state in shared_states]
     check_same_shapes(updates)
     engine = engine_for(device)
-    # substrafl_amd's own schemas already need this package to unpickle: the flat wire format
-    return engine.fedavg(updates, n_samples, wire=wire)
+    # substrafl_amd's own schemas already need this package to unpickle: the flat wire format.
+    # fedavg_routed where the engine has it: fedavg, plus wire.BF16 states on the multi-GPU and
+    # out-of-core routes, which fedavg itself refuses
+    return getattr(engine, "fedavg_routed", engine.fedavg)(updates, n_samples, wire=wire)
