@@ -1,0 +1,85 @@
+/*
+ * fedagg_dense.h -- C ABI of libfedagg_dense.so: a dense fp64 LU solve on MI355X (gfx950) for
+ * NewtonRaphson's Newton system (substrafl/strategies/newton_raphson.py:213,
+ * `np.linalg.solve(total_hessians, total_gradient_one_d)`).
+ *
+ * A library of its own beside libfedagg.so: nothing in fedagg.h changes, and the aggregation
+ * engine loads this one only when a caller opts in (integration.accelerate(..., solve="device")).
+ * The default stays the reference's host solve, bit for bit.
+ *
+ * Accuracy contract (u = 2^-53, gamma_n = n u / (1 - n u)).  Unlike fedagg.h, nothing here is
+ * bit-identical to NumPy: a device LU cannot reproduce LAPACK's rounding, and LAPACK's own bits
+ * differ between BLAS builds.  What is promised instead:
+ *   - partial pivoting: at step j the pivot is the first row i >= j of largest |a_ij|, so every
+ *     multiplier satisfies |l_ij| <= 1;
+ *   - the factors satisfy the componentwise bound |P A - L U| <= gamma_n |L| |U| (Higham, Accuracy
+ *     and Stability of Numerical Algorithms, thm 9.3: any summation order, with or without FMA);
+ *   - for matrices whose growth factor is of order 1 the solution's normwise backward error
+ *     ||b - A x||inf / (||A||inf ||x||inf + ||b||inf) is at most n u (tests/test_dense_solve_gpu.py);
+ *   - results are deterministic: the same build gives the same bits on every run and stream
+ *     (no atomics, every sum in a fixed order; contraction to FMA is allowed).
+ * Inputs with NaN or Inf raise nothing and fault nothing; their outputs are unspecified.
+ *
+ * Conventions (those of fedagg.h)
+ *   - d_* are device pointers owned by the caller; matrices are ROW-major with a leading dimension
+ *     of lda >= n ELEMENTS; elements [n, lda) of a row are never read or written.
+ *   - `stream` is a hipStream_t (NULL = the legacy default stream); every call is asynchronous on
+ *     it, allocates nothing and never synchronises the host: the launch sequence is a function of
+ *     n alone, the kernels are ordered by the stream alone.
+ *   - Every argument is checked before the first HIP call.  Return: 0, or a negative code with
+ *     fedagg_dense_last_error() giving the calling thread's message.
+ *   - n == 0 returns FEDAGG_DENSE_OK and touches nothing.
+ */
+#ifndef FEDAGG_DENSE_H
+#define FEDAGG_DENSE_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define FEDAGG_DENSE_ABI_VERSION 1
+#define FEDAGG_DENSE_MAX_N (1u << 20) /* an 8 TiB matrix: beyond any HBM, keeps every grid in range */
+
+enum {
+  FEDAGG_DENSE_OK = 0,
+  FEDAGG_DENSE_EINVAL = -1, /* bad argument (NULL pointer, lda < n, size overflow, ...) */
+  FEDAGG_DENSE_EHIP = -2,   /* a HIP runtime call failed                                */
+};
+
+int fedagg_dense_abi_version(void);
+const char* fedagg_dense_last_error(void);
+
+/* The blocking the kernels use: `panel` columns are factored at a time (also the block of the
+ * triangular solves and of the substitutions), the trailing update works on tile_m x tile_n
+ * tiles.  Sizes next to these and their multiples are where the kernels change path. */
+int fedagg_dense_blocking(int* panel, int* tile_m, int* tile_n);
+
+/* Bytes of device workspace fedagg_dense_getrf_f64 / fedagg_dense_solve_f64 need for order n
+ * (may be 0: d_ws may then be NULL). */
+uint64_t fedagg_dense_ws_bytes(uint64_t n);
+
+/* In-place LU with partial pivoting, P A = L U (blocked, right-looking; the trailing update on
+ * v_mfma_f64_16x16x4_f64).  L is unit lower triangular, stored below the diagonal; U on and
+ * above it.  d_ipiv[j] (0-based, in [j, n)) is the row interchanged with row j at step j.
+ * *d_info is 0, or j + 1 for the first exactly-zero pivot u_jj: the factorisation then goes on
+ * as LAPACK's does (no fault), and what it leaves in d_A is unspecified. */
+int fedagg_dense_getrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipiv, int32_t* d_info, void* d_ws,
+                           void* stream);
+
+/* Solve A x = b from the factors of fedagg_dense_getrf_f64, one right-hand side, in place in d_b:
+ * the interchanges, then blocked forward (L) and back (U) substitution. */
+int fedagg_dense_getrs_f64(const double* d_LU, uint64_t n, uint64_t lda, const int32_t* d_ipiv, double* d_b,
+                           void* stream);
+
+/* fedagg_dense_getrf_f64 then fedagg_dense_getrs_f64.  With *d_info != 0 afterwards d_b holds
+ * unspecified values (divisions by the zero pivot), as d_A does. */
+int fedagg_dense_solve_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipiv, int32_t* d_info, double* d_b,
+                           void* d_ws, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* FEDAGG_DENSE_H */

@@ -1036,9 +1036,22 @@ class AggregationEngine:
         rounded back into client 0's type (``fedagg_cast``).  Every client's layers must share one
         product type (a concatenated gradient is one array)."""
         rows = native_byte_order(rows)
-        K, L = len(rows), len(rows[0])
-        if L == 0:
+        if len(rows[0]) == 0:
             return []
+        d_out, layout = self._sequential_sum_device(rows, n_samples, self._B_OUT)
+        tm = self.last_timing
+        out = runtime.reusable_host_array(layout.M, layout.dtype, "seqsum")
+        self.session().fetch(d_out, out)
+        tm["total_s"] = time.perf_counter() - tm.pop("_t0")
+        return [arr for _, arr in layout.unpack(out, wire)]
+
+    def _sequential_sum_device(self, rows: List[List[np.ndarray]], n_samples: Sequence[int], out_slot: int):
+        """:meth:`sequential_sum` up to its fetch: the total is left in session buffer ``out_slot``
+        (flat, ``layout.M`` elements of ``layout.dtype``, ordered on the session stream).  Returns
+        ``(device pointer, layout)``; the staging uses the bucket slot and, for mixed client
+        dtypes, the ``cv`` and ``c`` slots, so ``out_slot`` must be none of those.  ``rows`` in
+        native byte order, at least one layer."""
+        K, L = len(rows), len(rows[0])
         reject_bf16(rows, "sequential_sum")
         pdt = []
         for row in rows:
@@ -1069,7 +1082,7 @@ class AggregationEngine:
             for k in range(K):
                 self._stage_rows(s, [rows[k]], BucketLayout(list(range(L)), shapes, pdt[k]), d_bucket + k * stride)
         tm["stage_s"] = time.perf_counter() - t0
-        d_out = s.buffer(self._B_OUT, stride)
+        d_out = s.buffer(out_slot, stride)
         s.scale_cast(d_bucket, T0, coeff[0], d_out, T0, M)
         k = 1
         while k < K:
@@ -1092,11 +1105,81 @@ class AggregationEngine:
                 self._chain(s, kind_of(P), [d_p], [1.0], M, d_acc)
                 s.cast(d_acc, P, d_out, T0, M)  # rounded back into client 0's type
             k += 1
-        out = runtime.reusable_host_array(M, T0, "seqsum")
-        s.fetch(d_out, out)
-        tm["total_s"] = time.perf_counter() - t0
+        tm["_t0"] = t0
         tm["mixed_dtypes"] = not uniform
-        return [arr for _, arr in layout.unpack(out, wire)]
+        return d_out, layout
+
+    # session events of newton_raphson_solve: start, sums done, factorisation done, substitution done
+    _EV_NR = (0, 1, 2, 3)
+
+    @serialized
+    def newton_raphson_solve(self, hessians: List[List[np.ndarray]], gradients: List[List[np.ndarray]],
+                             n_samples: Sequence[int]):
+        """NewtonRaphson's Newton system solved on the device (opt-in; newton_raphson.py:195-213):
+        the Hessian and gradient sums exactly as :meth:`sequential_sum` makes them, left in two
+        session buffers, then ``fedagg_dense_solve_f64`` (include/fedagg_dense.h: blocked LU with
+        partial pivoting, held to backward-error bounds, not to LAPACK's bits) on the session
+        stream, and a fetch of the P doubles of ``x`` and of ``info`` -- the P x P sum never
+        comes home.  ``hessians[k] = [H_k]`` (P x P), ``gradients[k] = [g_k]`` (P,).
+
+        Returns ``(x, info, reason)``: ``x`` float64 of P elements with ``info`` 0 or j + 1 for a
+        first exactly-zero pivot, or ``(None, 0, reason)`` when the sums are not a float64 Hessian
+        with a float32 / float64 gradient -- NumPy solves those in another precision or refuses
+        them, so the caller takes the host solve (nothing has run then).  An fp32 gradient sum is
+        widened to fp64 by ``fedagg_cast``, exactly, as NumPy promotes ``solve(f64, f32)``."""
+        from . import _native_dense
+
+        hessians, gradients = native_byte_order(hessians), native_byte_order(gradients)
+        h0, g0 = np.asarray(hessians[0][0]), np.asarray(gradients[0][0])
+        ht, gt = np.result_type(h0.dtype, 1.0), np.result_type(g0.dtype, 1.0)
+        if ht != np.float64:
+            return None, 0, f"host: {np.dtype(ht).name} Hessian sum (NumPy's solve is not a float64 one)"
+        if gt not in (np.float32, np.float64):
+            return None, 0, f"host: {np.dtype(gt).name} gradient sum"
+        if h0.ndim != 2 or h0.shape[0] != h0.shape[1] or g0.ndim != 1 or g0.shape[0] != h0.shape[0]:
+            return None, 0, f"host: shapes {h0.shape} / {g0.shape} (NumPy's own error applies)"
+        P = int(h0.shape[0])
+        if P == 0:
+            return None, 0, "host: empty system"
+        lib = _native_dense.load()
+        s = self.session()
+        t0 = time.perf_counter()
+        ev = self._EV_NR
+        s.event_record(ev[0])
+        d_h, _ = self._sequential_sum_device(hessians, n_samples, self._B_OUT)
+        tm_h = self.last_timing
+        d_g, lay_g = self._sequential_sum_device(gradients, n_samples, self._B_COUT)
+        tm_g = self.last_timing
+        if lay_g.dtype != np.float64:
+            d_b = s.buffer(self._B_TMP, P * 8)
+            s.cast(d_g, lay_g.dtype, d_b, np.float64, P)
+        else:
+            d_b = d_g
+        s.event_record(ev[1])
+        ws_bytes = int(lib.fedagg_dense_ws_bytes(P))
+        d_int = s.buffer(self._B_CNT, (P + 1) * 4)  # ipiv, then info
+        d_ws = s.buffer(self._B_WS, ws_bytes) if ws_bytes else 0
+        s._bump(d_h)
+        s._bump(d_b)
+        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
+        _native_dense.check(lib.fedagg_dense_getrf_f64(vp(d_h), P, P, vp(d_int), vp(d_int + 4 * P), vp(d_ws), st),
+                            "dense_getrf_f64")
+        s.event_record(ev[2])
+        _native_dense.check(lib.fedagg_dense_getrs_f64(vp(d_h), P, P, vp(d_int), vp(d_b), st), "dense_getrs_f64")
+        s.event_record(ev[3])
+        s.sync()  # so that fetch_s below is the fetch alone, not the wait for the kernels
+        t1 = time.perf_counter()
+        x = np.empty(P, np.float64)
+        s.fetch(d_b, x)
+        info = np.empty(1, np.int32)
+        s.fetch(d_int + 4 * P, info)
+        t2 = time.perf_counter()
+        self.last_timing = {
+            "solve": "device", "P": P, "stage_s": tm_h.get("stage_s", 0.0) + tm_g.get("stage_s", 0.0),
+            "mixed_dtypes": bool(tm_h.get("mixed_dtypes") or tm_g.get("mixed_dtypes")),
+            "sums_ms": s.event_elapsed_ms(ev[0], ev[1]), "factor_ms": s.event_elapsed_ms(ev[1], ev[2]),
+            "substitute_ms": s.event_elapsed_ms(ev[2], ev[3]), "fetch_s": t2 - t1, "total_s": t2 - t0}
+        return x, int(info[0]), "device"
 
     @staticmethod
     def _chain(s, kind: str, ptrs: List[int], coeffs: List[float], M: int, d_acc: int) -> None:

@@ -15,7 +15,10 @@ everything of it -- constructor, ``name``, graph building (``build_compute_plan`
   reduction (+ the reference's ``np.linalg.qr`` of each averaged matrix);
 * ``NewtonRaphson.compute_averaged_states`` (newton_raphson.py:151-216): the weighted sums of the
   clients' Hessians and gradients (the explicit ``+=`` chain, ``engine.sequential_sum``), then the
-  reference's own ``np.linalg.solve`` and unflatten on the host.
+  reference's own ``np.linalg.solve`` and unflatten on the host.  Opt-in, ``accelerate(NewtonRaphson,
+  solve="device")`` or ``FEDAGG_NR_SOLVE=device``: the dense solve on the GPU too (fp64 LU with
+  partial pivoting, ``libfedagg_dense.so``), held to backward-error bounds instead of LAPACK's bits
+  (include/fedagg_dense.h); the default is unchanged.
 
 So the class goes straight into ``simulate_experiment`` / ``execute_experiment``::
 
@@ -35,6 +38,7 @@ built ``libfedagg.so``) next to ``substrafl``.  Nothing here imports SubstraFL a
 from __future__ import annotations
 
 import importlib
+import os
 from typing import Optional
 
 import numpy as np
@@ -56,10 +60,24 @@ def _reference_modules(strategy_cls):
             importlib.import_module(f"{pkg}.remote").remote, importlib.import_module(f"{pkg}.exceptions"))
 
 
-def accelerate(strategy_cls, device: Devices = None):
+def _solve_mode(solve: str) -> str:
+    """``solve`` (``"host"`` or ``"device"``) under the environment override ``FEDAGG_NR_SOLVE``."""
+    mode = os.environ.get("FEDAGG_NR_SOLVE") or solve
+    if mode not in ("host", "device"):
+        raise ValueError(f"solve must be 'host' or 'device', not {mode!r}")
+    return mode
+
+
+def accelerate(strategy_cls, device: Devices = None, solve: str = "host"):
     """A subclass of the reference strategy class ``strategy_cls`` (``FedAvg``, ``Scaffold``,
-    ``FedPCA`` or a subclass of one of them) whose aggregation methods run on the engine of
-    ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or "all")."""
+    ``FedPCA``, ``NewtonRaphson`` or a subclass of one of them) whose aggregation methods run on the
+    engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
+    "all").  ``solve`` matters for NewtonRaphson only: ``"host"`` (the default) keeps the
+    reference's ``np.linalg.solve``, bit for bit; ``"device"`` solves the Newton system on the GPU
+    as well (:func:`newton_raphson_update`).  ``FEDAGG_NR_SOLVE=device|host`` overrides it, read
+    when the aggregation runs."""
+    if solve not in ("host", "device"):
+        raise ValueError(f"solve must be 'host' or 'device', not {solve!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
     empty = exceptions.EmptySharedStatesError
     base_init = strategy_cls.__init__
@@ -119,12 +137,14 @@ def accelerate(strategy_cls, device: Devices = None):
 
         def compute_averaged_states(self, shared_states):
             """newton_raphson.py:151-216: the reference's checks, the two weighted sums on the
-            engine, then the reference's own dense solve and unflatten on the host."""
+            engine, then the reference's own dense solve on the host (``solve="host"``) or the
+            fp64 LU on the device (``solve="device"``), and the reference's unflatten."""
             self._check_shared_states(shared_states)
-            hessian, gradient = newton_raphson_sums(shared_states, self._fedagg_device)
-            update = -self._damping_factor * np.linalg.solve(hessian, gradient)
+            update = newton_raphson_update(shared_states, self._damping_factor, self._fedagg_device,
+                                           solve=self._fedagg_solve)
             return averaged_cls(parameters_update=self._unflatten_array(update, shared_states[-1].gradients))
 
+        ns["_fedagg_solve"] = solve
         ns["compute_averaged_states"] = remote(compute_averaged_states)
         ns["_aggregation_methods"] = {"compute_averaged_states": "sequential"}
     else:
@@ -136,13 +156,9 @@ def accelerate(strategy_cls, device: Devices = None):
     return cls
 
 
-def newton_raphson_sums(shared_states, device: Optional[Devices] = None):
-    """The weighted Hessian and gradient sums of NewtonRaphson.compute_averaged_states
-    (newton_raphson.py:195-211) on the engine (:meth:`engine.AggregationEngine.sequential_sum`:
-    the explicit ``+=`` chain from client 0's product, bit for bit).  Returns ``(total_hessians,
-    total_gradient_one_d)``; the gradients are concatenated per client first, as there.
-    ``ZeroDivisionError`` for ``sum(n_samples) == 0`` and ``ValueError`` for sizes that differ
-    between clients, before any device work."""
+def _newton_raphson_rows(shared_states):
+    """``(hessians, gradients, n_samples)`` as :meth:`engine.AggregationEngine.sequential_sum` takes
+    them, after the reference's host-side errors (newton_raphson.py:195-211)."""
     n_samples = [s.n_samples for s in shared_states]
     if sum(int(n) for n in n_samples) == 0:
         raise ZeroDivisionError("division by zero")  # n_samples / n_all_samples (:201)
@@ -150,6 +166,50 @@ def newton_raphson_sums(shared_states, device: Optional[Devices] = None):
     gradients = [[np.concatenate([np.asarray(g).reshape(-1) for g in s.gradients])] for s in shared_states]
     check_same_shapes(hessians)  # total_hessians += ... (:208)
     check_same_shapes(gradients)
+    return hessians, gradients, n_samples
+
+
+def newton_raphson_update(shared_states, damping_factor, device: Optional[Devices] = None, solve: str = "device"):
+    """The flat parameter update of NewtonRaphson.compute_averaged_states (newton_raphson.py:195-213),
+    ``-damping_factor * solve(sum_k c_k H_k, sum_k c_k g_k)``, for any strategy object or host.
+
+    ``solve="host"``: :func:`newton_raphson_sums`, then ``np.linalg.solve`` -- the reference's bits.
+    ``solve="device"``: the sums stay in HBM and ``fedagg_dense_solve_f64`` solves the system there
+    (:meth:`engine.AggregationEngine.newton_raphson_solve`); only the P doubles of ``x`` come home.
+    The sums are the same bits either way; ``x`` is then within the backward-error bounds of
+    include/fedagg_dense.h instead of LAPACK's rounding, and deterministic run to run.  The device
+    route needs a float64 Hessian sum and a float32 or float64 gradient sum; anything else (an fp32
+    Hessian, which NumPy solves in single precision; fp16, which it refuses) takes the host solve
+    and says why in ``last_timing["solve"]``.  An exactly-zero pivot raises NumPy's
+    ``LinAlgError("Singular matrix")``.  NaN or Inf in the inputs raise nothing, as with NumPy;
+    what they give is unspecified.  ``FEDAGG_NR_SOLVE`` overrides ``solve``."""
+    mode = _solve_mode(solve)
+    hessians, gradients, n_samples = _newton_raphson_rows(shared_states)
+    eng = engine_for(device)
+    eng = eng._single() if hasattr(eng, "_single") else eng  # several GPUs: the first one, as for the sums
+    reason = "host"
+    if mode == "device":
+        x, info, reason = eng.newton_raphson_solve(hessians, gradients, n_samples)
+        if x is not None:
+            if info != 0:
+                raise np.linalg.LinAlgError("Singular matrix")
+            return -damping_factor * x
+    (total_h,) = eng.sequential_sum(hessians, n_samples)
+    (total_g,) = eng.sequential_sum(gradients, n_samples)
+    update = -damping_factor * np.linalg.solve(total_h, total_g)
+    if isinstance(getattr(eng, "last_timing", None), dict):  # (an engine stand-in may keep no timing)
+        eng.last_timing["solve"] = reason
+    return update
+
+
+def newton_raphson_sums(shared_states, device: Optional[Devices] = None):
+    """The weighted Hessian and gradient sums of NewtonRaphson.compute_averaged_states
+    (newton_raphson.py:195-211) on the engine (:meth:`engine.AggregationEngine.sequential_sum`:
+    the explicit ``+=`` chain from client 0's product, bit for bit).  Returns ``(total_hessians,
+    total_gradient_one_d)``; the gradients are concatenated per client first, as there.
+    ``ZeroDivisionError`` for ``sum(n_samples) == 0`` and ``ValueError`` for sizes that differ
+    between clients, before any device work."""
+    hessians, gradients, n_samples = _newton_raphson_rows(shared_states)
     eng = engine_for(device)
     (total_h,) = eng.sequential_sum(hessians, n_samples)
     (total_g,) = eng.sequential_sum(gradients, n_samples)
