@@ -1,5 +1,5 @@
 """Build hook of the installable package (pyproject.toml): ``build_py`` also compiles
-``libfedagg.so`` and ``libfedagg_dense.so`` for gfx950 into the build tree with the same compiler, flags and object cache as
+``libfedagg.so``, ``libfedagg_dense.so`` and ``libfedagg_promote.so`` for gfx950 into the build tree with the same compiler, flags and object cache as
 ``__graft_entry__.build()``, so the wheel carries the HIP library next to the Python package.
 No hipcc, no wheel: ``compile_library`` raises, and the build fails loudly."""
 
@@ -22,6 +22,7 @@ class BuildPyWithHip(build_py):
         pkg = Path(self.build_lib).resolve() / "substrafl_amd"
         __graft_entry__.compile_library(pkg / "libfedagg.so")
         __graft_entry__.compile_dense_library(pkg / "libfedagg_dense.so")
+        __graft_entry__.compile_promote_library(pkg / "libfedagg_promote.so")
 
 
 class BinaryDistribution(Distribution):

@@ -18,6 +18,16 @@ tensors torch computes each op in fp32 and rounds its result once to the tensor'
 model takes an fp32 update (the aggregator's average of ``wire.BF16`` buckets) with the add in the
 promoted fp32, as torch on ROCm performs it on the reference's per-layer tensors (the update
 rounded to bf16 first in each full 16384-element block of a layer; include/fedagg.h states the rules).
+
+A 16-bit model next to fp64 operands -- a Scaffold client from round 2 on, once the aggregator's
+fp64 ``avg_parameters_update`` and ``server_control_variate`` have come back -- follows torch's
+type promotion on ``libfedagg_promote.so`` (include/fedagg_promote.h states the rules):
+``increment_parameters`` of 16-bit parameters by an fp64 update is one
+``fedagg_promote_increment`` launch, ``weighted_sum_parameters`` over lists that are each the
+model's 16-bit kind or fp64 (at least one of each) one ``fedagg_promote_wsum`` launch into a
+fresh fp64 bucket, bit for bit what torch on the device gives for the reference's per-layer
+tensors (an fp16 layer's trailing ``numel mod 2048`` elements included, where torch rounds the
+product once).  ``FEDAGG_FLAT_PROMOTE=0`` keeps those operand sets on the torch loops.
 """
 
 from __future__ import annotations
@@ -29,7 +39,7 @@ import numpy as np
 import torch
 from torch._utils import _unflatten_dense_tensors
 
-from .. import _native
+from .. import _native, _native_promote
 from ..wire import BF16, bucket_views, flat_of
 
 _BN = (
@@ -187,6 +197,13 @@ def increment_parameters(
                                                              float(updates_multiplier), _stream(flat.device)),
                               "flat_increment_kind")
                 return
+            if flat is not None and flat.dtype == torch.float64 and _native_promote.enabled():
+                # torch's promotion: the sum in fp64, back to the parameters' kind through float
+                lib = _native_promote.load()
+                _native_promote.check(lib.fedagg_promote_increment(
+                    _native.ptr_array([p.data.data_ptr() for p in params]), pkind, _numel_array(params), len(params),
+                    flat.data_ptr(), float(updates_multiplier), _stream(flat.device)), "flat_promote_increment")
+                return
         elif pkind == _native.FEDAGG_F32:
             flat = _device_flat(updates, params[0].device)
             if flat is not None and flat.dtype in (torch.float32, torch.float64):
@@ -276,7 +293,7 @@ def weighted_sum_parameters(parameters_list: List[List[torch.Tensor]], coefficie
             parameters_to_sum[0].data.shape == parameter.data.shape for parameter in parameters_to_sum
         ), "The shape of the parameters are unequal."
     kinds = [_kind(lst, parameters_list[0][0].device if parameters_list[0] else None) for lst in parameters_list]
-    # a 16-bit list next to a list of another kind follows torch's promotion: left to torch
+    # a 16-bit list next to a list of another kind follows torch's promotion: the promoted ops below, or torch
     if 1 <= len(parameters_list) <= _native.FEDAGG_FLAT_MAX_LISTS and all(k is not None for k in kinds) and (
             not any(k in _KIND16 for k in kinds) or len(set(kinds)) == 1):
         like = parameters_list[0]
@@ -292,6 +309,20 @@ def weighted_sum_parameters(parameters_list: List[List[torch.Tensor]], coefficie
                                                (ctypes.c_int * len(kinds))(*kinds), len(parameters_list), coeffs,
                                                _numel_array(like), len(like), out.data_ptr(), _KIND[out_dtype],
                                                _stream(out.device)), "flat_wsum")
+        return _views(out, like)
+    # lists that are each ONE 16-bit kind or fp64, at least one of each: torch's promotion, result fp64
+    if (1 <= len(parameters_list) <= _native.FEDAGG_FLAT_MAX_LISTS and all(k is not None for k in kinds)
+            and _native.FEDAGG_F64 in kinds and len(set(kinds) - {_native.FEDAGG_F64}) == 1
+            and (set(kinds) & set(_KIND16)) and _native_promote.enabled()):
+        like = parameters_list[0]
+        with torch.no_grad():
+            out = torch.empty(sum(t.numel() for t in like), dtype=torch.float64, device=like[0].device)
+            lib = _native_promote.load()
+            coeffs = (ctypes.c_double * len(coefficient_list))(*[float(c) for c in coefficient_list])
+            _native_promote.check(lib.fedagg_promote_wsum(
+                _native.ptr_array([t.data_ptr() for lst in parameters_list for t in lst]),
+                (ctypes.c_int * len(kinds))(*kinds), len(parameters_list), coeffs, _numel_array(like), len(like),
+                out.data_ptr(), _stream(out.device)), "flat_promote_wsum")
         return _views(out, like)
     weighted_sum = []
     for parameters_to_sum in zip(*parameters_list):
