@@ -1,7 +1,8 @@
 /*
  * fedagg_dense.h -- C ABI of libfedagg_dense.so: a dense fp64 LU solve on MI355X (gfx950) for
  * NewtonRaphson's Newton system (substrafl/strategies/newton_raphson.py:213,
- * `np.linalg.solve(total_hessians, total_gradient_one_d)`).
+ * `np.linalg.solve(total_hessians, total_gradient_one_d)`), and a dense fp64 Cholesky
+ * factorisation for its clients' Hessian check (torch_newton_raphson_algo.py:346-352).
  *
  * A library of its own beside libfedagg.so: nothing in fedagg.h changes, and the aggregation
  * engine loads this one only when a caller opts in (integration.accelerate(..., solve="device")).
@@ -16,6 +17,10 @@
  *     and Stability of Numerical Algorithms, thm 9.3: any summation order, with or without FMA);
  *   - for matrices whose growth factor is of order 1 the solution's normwise backward error
  *     ||b - A x||inf / (||A||inf ||x||inf + ||b||inf) is at most n u (tests/test_dense_solve_gpu.py);
+ *   - the Cholesky factor of fedagg_dense_potrf_f64 satisfies |A - L L^T| <= gamma_{n+1} |L| |L^T|
+ *     on the lower triangle (Higham thm 10.3: any summation order, with or without FMA; fp64
+ *     sqrt and division are correctly rounded), so a run that ends with *d_info == 0 proves A + E
+ *     positive definite for an E within that bound (tests/test_dense_potrf_gpu.py);
  *   - results are deterministic: the same build gives the same bits on every run and stream
  *     (no atomics, every sum in a fixed order; contraction to FMA is allowed).
  * Inputs with NaN or Inf raise nothing and fault nothing; their outputs are unspecified.
@@ -78,6 +83,17 @@ int fedagg_dense_getrs_f64(const double* d_LU, uint64_t n, uint64_t lda, const i
  * unspecified values (divisions by the zero pivot), as d_A does. */
 int fedagg_dense_solve_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipiv, int32_t* d_info, double* d_b,
                            void* d_ws, void* stream);
+
+/* In-place lower Cholesky, A = L L^T (blocked, right-looking; the trailing update on
+ * v_mfma_f64_16x16x4_f64 over the tiles on and below the diagonal).  Only elements with row >=
+ * column are read, and L is written there: the strict upper triangle, like elements [n, lda) of a
+ * row, is never read or written.  Needs no workspace.
+ * *d_info is 0 -- the certificate that A (its lower triangle mirrored) is positive definite to
+ * within the backward error above -- or j + 1 for the first pivot d = a_jj - sum_k l_jk^2 that is
+ * not > 0 (a NaN counts, as in LAPACK's dpotrf) or is +Inf.  The factorisation then goes on, on
+ * whatever values there are (no fault): rows and columns [0, j) of L, the leading triangle, are
+ * the factor's, everything else in the lower triangle is unspecified. */
+int fedagg_dense_potrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_info, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ SIGNATURES = {
     "fedagg_dense_getrf_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void, c_void, c_void]),
     "fedagg_dense_getrs_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void, c_void]),
     "fedagg_dense_solve_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void, c_void, c_void, c_void]),
+    "fedagg_dense_potrf_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void]),
 }
 
 ABI_VERSION = 1

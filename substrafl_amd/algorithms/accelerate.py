@@ -2,7 +2,8 @@
 weight-delta producer / consumer of ``train`` on libfedagg's flat-bucket kernels (SURVEY.md §8(a)
 rows a5-a7, §8(f) rows 1 and 3).
 
-``accelerate_algo(TorchFedAvgAlgo)`` (or ``TorchScaffoldAlgo``, or any user subclass of either)
+``accelerate_algo(TorchFedAvgAlgo)`` (or ``TorchScaffoldAlgo`` or ``TorchNewtonRaphsonAlgo``, or any
+user subclass of one)
 returns a subclass that keeps everything of the class -- constructor, ``_local_train``,
 ``predict``, checkpointing, ``strategies`` and the reference's ``@remote_data`` decorator -- and
 replaces only the steps of ``train`` that move the model's weights around:
@@ -16,7 +17,13 @@ replaces only the steps of ``train`` that move the model's weights around:
   in with one H2D copy (:403-406), ``delta_variate`` / ``control_variate_update`` / the client
   cv step as fused ``fedagg_flat_wsum`` launches (:416-420, :451-466) and the per-step
   ``w += lr * delta_variate`` hook (:256-268) as one ``fedagg_flat_increment`` launch per
-  optimizer step.
+  optimizer step;
+* NewtonRaphson (torch_newton_raphson_algo.py:280-359): the averaged update onto the model in one
+  H2D copy plus one ``fedagg_flat_increment`` launch (:328-333), and, opt-in with
+  ``hessian_check="device"``, the eigenvalue check of :346-352 preceded by a Cholesky certificate
+  on the GPU (``libfedagg_dense.so``; :func:`..integration.newton_raphson_hessian_check`), which
+  accepts a positive definite Hessian without computing an eigenvalue.  The autograd Hessian and
+  its accumulation stay the class's own; the default keeps the reference's check as it is.
 
 The order of operations, the assertions and the error types are the reference's; every result
 is bit-identical to the reference's torch ops (weight_manager.py semantics, see
@@ -45,7 +52,8 @@ import importlib
 
 from . import weight_manager as wm
 
-_BASES = {"TorchFedAvgAlgo": "fedavg", "TorchScaffoldAlgo": "scaffold"}
+_BASES = {"TorchFedAvgAlgo": "fedavg", "TorchScaffoldAlgo": "scaffold", "TorchNewtonRaphsonAlgo": "newton_raphson"}
+_MODULES = ("torch_fed_avg_algo", "torch_scaffold_algo", "torch_newton_raphson_algo")
 
 
 def _reference_base(algo_cls):
@@ -53,11 +61,10 @@ def _reference_base(algo_cls):
     if not isinstance(algo_cls, type):
         raise TypeError(f"accelerate_algo takes a class, not {algo_cls!r}")
     for base in algo_cls.__mro__:
-        if base.__name__ in _BASES and base.__module__.rsplit(".", 1)[-1] in ("torch_fed_avg_algo",
-                                                                               "torch_scaffold_algo"):
+        if base.__name__ in _BASES and base.__module__.rsplit(".", 1)[-1] in _MODULES:
             return base
-    raise TypeError(f"accelerate_algo takes SubstraFL's TorchFedAvgAlgo or TorchScaffoldAlgo (or a subclass), "
-                    f"not {algo_cls!r}")
+    raise TypeError(f"accelerate_algo takes SubstraFL's TorchFedAvgAlgo, TorchScaffoldAlgo or TorchNewtonRaphsonAlgo "
+                    f"(or a subclass), not {algo_cls!r}")
 
 
 def _export(self, tensors, tag="export"):
@@ -157,6 +164,48 @@ def _scaffold_train(shared_state_cls, fast_rule, update_error):
     return train
 
 
+def _newton_raphson_train(shared_state_cls, error_cls):
+    def train(self, data_from_opener, shared_state=None):
+        """TorchNewtonRaphsonAlgo.train (torch_newton_raphson_algo.py:280-359): the averaged update
+        goes onto the model in one H2D copy plus one ``fedagg_flat_increment`` launch (:328-333),
+        and the eigenvalue check of :346-352 is :func:`..integration.newton_raphson_hessian_check`
+        (``hessian_check="device"``: a Cholesky certificate on the GPU first).  ``_local_train``,
+        the autograd Hessian and its accumulation are the class's own."""
+        from ..integration import newton_raphson_hessian_check
+
+        train_dataset = self._dataset(data_from_opener, is_inference=False)
+        if shared_state is None:
+            self._index_generator = self._instantiate_index_generator(len(train_dataset))
+        else:
+            assert self._index_generator.n_samples is not None
+            # the host layers go over as one bucket; w += 1.0 * u in one launch
+            wm.increment_parameters(self._model, list(shared_state.parameters_update),
+                                    with_batch_norm_parameters=self._with_batch_norm_parameters)
+        gen = self._index_generator
+        gen.reset_counter()
+
+        self._model.train()
+        self._final_gradients, self._final_hessian, self._n_samples_done = self._initialize_gradients_and_hessian()
+        self._local_train(train_dataset)
+        # every sample exactly once before the next update
+        assert gen.n_samples == self._n_samples_done
+
+        self._fedagg_hessian_route = newton_raphson_hessian_check(
+            self._final_hessian, self._l2_coeff, device=_device_index(self._device), check=self._fedagg_hessian_check,
+            error_cls=error_cls)
+        gen.check_num_updates()
+        return shared_state_cls(n_samples=gen.n_samples, hessian=self._final_hessian,
+                                gradients=self._final_gradients)
+
+    return train
+
+
+def _device_index(device):
+    """The engine device of a torch device: its index, or None (the current GPU; also for a CPU
+    model, whose Hessian check may still run on the GPU when asked to)."""
+    return device.index if getattr(device, "type", None) == "cuda" else None
+
+
 def _frozen_source(host: list, tensors):
     """Simulation mode with the device hand-off (``handoff``): the server control variate's host
     arrays as received, when they are frozen (an engine output) -- the client's export of c may
@@ -207,11 +256,21 @@ def _registering_init(base_init):
     return __init__
 
 
-def accelerate_algo(algo_cls, wire: bool = False):
-    """A subclass of ``algo_cls`` (SubstraFL's ``TorchFedAvgAlgo`` / ``TorchScaffoldAlgo`` or a
-    subclass of one) whose ``train`` moves weights with the flat-bucket kernels.  ``wire``:
-    export :class:`..wire.BucketArray` layers instead of plain arrays."""
+def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
+    """A subclass of ``algo_cls`` (SubstraFL's ``TorchFedAvgAlgo`` / ``TorchScaffoldAlgo`` /
+    ``TorchNewtonRaphsonAlgo`` or a subclass of one) whose ``train`` moves weights with the
+    flat-bucket kernels.  ``wire``: export :class:`..wire.BucketArray` layers instead of plain
+    arrays.  ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
+    default, keeps the reference's eigenvalue check and never loads the dense library;
+    ``"device"`` tries a Cholesky certificate on the GPU first
+    (:func:`..integration.newton_raphson_hessian_check`; ``FEDAGG_NR_CHECK`` overrides it when
+    ``train`` runs)."""
     base = _reference_base(algo_cls)
+    kind = _BASES[base.__name__]
+    if kind != "newton_raphson" and hessian_check is not None:
+        raise TypeError(f"hessian_check is an option of TorchNewtonRaphsonAlgo, not of {base.__name__}")
+    if kind == "newton_raphson" and hessian_check not in (None, "host", "device"):
+        raise ValueError(f"hessian_check must be 'host' or 'device', not {hessian_check!r}")
     pkg = base.__module__.split(".")[0]
     remote_data = importlib.import_module(f"{pkg}.remote").remote_data
     schemas = importlib.import_module(f"{pkg}.strategies.schemas")
@@ -219,7 +278,13 @@ def accelerate_algo(algo_cls, wire: bool = False):
           "_fedagg_wire": bool(wire),
           "__init__": _registering_init(algo_cls.__init__),
           "__module__": __name__}  # type() under ABCMeta would otherwise record "abc"
-    if _BASES[base.__name__] == "scaffold":
+    if kind == "newton_raphson":
+        # the class users catch: the one the base's own module imported by name
+        error_cls = importlib.import_module(base.__module__).NegativeHessianMatrixError
+        ns["train"] = remote_data(_newton_raphson_train(schemas.NewtonRaphsonSharedState, error_cls))
+        ns["_fedagg_hessian_check"] = hessian_check or "host"
+        ns["_fedagg_hessian_route"] = None
+    elif kind == "scaffold":
         exceptions = importlib.import_module(f"{pkg}.exceptions")
         fast = importlib.import_module(base.__module__).CUpdateRule.FAST
         ns["train"] = remote_data(_scaffold_train(schemas.ScaffoldSharedState, fast,

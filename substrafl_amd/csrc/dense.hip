@@ -8,12 +8,10 @@
 //   dense_update_f64   A22 -= L21 U12 on v_mfma_f64_16x16x4_f64, DN_TM x DN_TN tiles through LDS,
 // then dense_perm_f64 / dense_fwd_f64 / dense_bwd_f64 for the right-hand side.  The stream orders
 // the kernels; no kernel waits on another workgroup, and no sum uses an atomic.
-#include <hip/hip_runtime.h>
+#include "dense_internal.h"
 
-#include <cstdio>
-
-#include "fedagg_dense.h"
-
+// (DN_NB, DN_TM, DN_TN and DN_BLOCK are dense_internal.h's, stated again here, where the tests of
+// the panel's strides read them; a difference is the compiler's "macro redefined")
 #define DN_NB 32               // panel width; block of the triangular solves and substitutions
 #define DN_TM 64               // trailing-update tile, rows
 #define DN_TN 64               // trailing-update tile, columns
@@ -22,24 +20,9 @@
 #define DN_BLOCK 256
 #define DN_UB 8                // rows a panel thread keeps in flight per step of the rank-1 update
 
-typedef double dn_f64x4 __attribute__((ext_vector_type(4)));
-typedef unsigned long long dn_u64;
+using namespace fedagg_dense_detail;  // g_error, fail, check_launch, check_matrix, blocks_for
 
 namespace {
-
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, long long v = 0) {
-  snprintf(g_error, sizeof(g_error), fmt, v);
-  return code;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return FEDAGG_DENSE_OK;
-  snprintf(g_error, sizeof(g_error), "%s: %s", what, hipGetErrorString(e));
-  return FEDAGG_DENSE_EHIP;
-}
 
 // (value, row) candidates of the pivot search: the larger value wins, the smaller row on a tie,
 // so the result is the first row of largest |a| whatever the order of the reduction.
@@ -359,17 +342,6 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_bwd_f64(const double* LU, dn_u
     }
     if (r >= 0) b[jb + (dn_u64)r] = ri;
   }
-}
-
-unsigned blocks_for(dn_u64 work) { return (unsigned)((work + DN_BLOCK - 1) / DN_BLOCK); }
-
-// The argument checks every entry point shares (n >= 1 here), before any HIP call.
-int check_matrix(const void* d_A, uint64_t n, uint64_t lda) {
-  if (!d_A) return fail(FEDAGG_DENSE_EINVAL, "d_A is NULL");
-  if (n > FEDAGG_DENSE_MAX_N) return fail(FEDAGG_DENSE_EINVAL, "n = %lld exceeds FEDAGG_DENSE_MAX_N", (long long)n);
-  if (lda < n) return fail(FEDAGG_DENSE_EINVAL, "lda = %lld is smaller than n", (long long)lda);
-  if (lda > UINT64_MAX / 8 / n) return fail(FEDAGG_DENSE_EINVAL, "n * lda * 8 overflows 64 bits (n = %lld)", (long long)n);
-  return FEDAGG_DENSE_OK;
 }
 
 int launch_getrf(double* A, dn_u64 n, dn_u64 lda, int32_t* ipiv, int32_t* info, hipStream_t st) {

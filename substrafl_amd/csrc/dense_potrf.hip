@@ -1,0 +1,176 @@
+// dense_potrf.hip -- libfedagg_dense.so: in-place fp64 lower Cholesky, A = L L^T, for gfx950
+// (include/fedagg_dense.h: the certificate of NewtonRaphson's Hessian check).  A blocked
+// right-looking factorisation that reads and writes the lower triangle only: per block column of
+// DN_NB columns
+//   dense_potrf_diag_f64    one workgroup factors the diagonal block in LDS and records the first
+//                           pivot that is not > 0,
+//   dense_potrf_panel_f64   L21 = A21 L11^-T (one thread per row, L11 from LDS),
+//   dense_potrf_update_f64  A22 -= L21 L21^T on v_mfma_f64_16x16x4_f64, the DN_TM x DN_TN tiles on
+//                           and below the diagonal only, both operands through LDS.
+// The stream orders the kernels; no kernel waits on another workgroup, no sum uses an atomic, and
+// no index or trip count depends on a matrix value: after a failed pivot everything still runs,
+// on whatever values (NaN) there are.
+#include "dense_internal.h"
+
+static_assert(DN_TM == DN_TN, "the trailing update walks square tiles on and below the diagonal");
+static_assert(DN_TM % DN_NB == 0, "a tile row starts on a panel boundary");
+
+using namespace fedagg_dense_detail;
+
+namespace {
+
+// Factor the nb x nb diagonal block at (j, j), right-looking, in LDS: per column c the pivot
+// d = a_cc - sum_k l_ck^2 (the sum already taken off by the steps before), l_cc = sqrt(d), the
+// column below it divided by l_cc, then the rank-1 update of the columns right of c.  !(d > 0)
+// also holds for a NaN, as in LAPACK's dpotrf; a pivot of +Inf fails as well (its square root
+// would zero the column below it and let the rest pass: no certificate of anything).  The first
+// such pivot of the whole factorisation stays in *info (the launch of j = 0 writes it
+// unconditionally, so the caller need not clear it).
+__global__ __launch_bounds__(DN_BLOCK) void dense_potrf_diag_f64(double* A, dn_u64 lda, dn_u64 j, int nb, int32_t* info) {
+  __shared__ double s[DN_NB][DN_NB + 1];
+  const int t = threadIdx.x;
+  for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
+    const int r = e / DN_NB, k = e % DN_NB;
+    s[r][k] = (k <= r && r < nb) ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
+  }
+  __syncthreads();
+  int32_t first = 0;  // thread 0's: 1-based index of the block's first failed pivot
+  for (int c = 0; c < nb; ++c) {
+    const double d = s[c][c];
+    if (t == 0 && (!(d > 0.0) || isinf(d)) && first == 0) first = (int32_t)(j + (dn_u64)c + 1);
+    const double l = sqrt(d);
+    __syncthreads();  // every thread has read d
+    if (t == c) s[c][c] = l;
+    if (t > c && t < nb) s[t][c] = s[t][c] / l;
+    __syncthreads();
+    for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
+      const int r = e / DN_NB, k = e % DN_NB;
+      if (k > c && k <= r && r < nb) s[r][k] = fma(-s[r][c], s[k][c], s[r][k]);
+    }
+    __syncthreads();
+  }
+  for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
+    const int r = e / DN_NB, k = e % DN_NB;
+    if (k <= r && r < nb) A[(j + (dn_u64)r) * lda + j + (dn_u64)k] = s[r][k];
+  }
+  if (t == 0) {
+    if (j == 0)
+      *info = first;
+    else if (first != 0 && *info == 0)
+      *info = first;
+  }
+}
+
+// L21 = A21 L11^-T below a full diagonal block (DN_NB columns): one thread per row, its DN_NB
+// values in registers, the lower triangle L11 (with its diagonal) broadcast from LDS; column k of
+// the row is (a_ik - sum_{m<k} l_im l_km) / l_kk, m ascending.
+__global__ __launch_bounds__(DN_BLOCK) void dense_potrf_panel_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
+  __shared__ double sL[DN_NB][DN_NB + 1];
+  for (int e = threadIdx.x; e < DN_NB * DN_NB; e += DN_BLOCK) {
+    const int r = e / DN_NB, k = e % DN_NB;
+    sL[r][k] = k <= r ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
+  }
+  __syncthreads();
+  const dn_u64 row = j + DN_NB + (dn_u64)blockIdx.x * DN_BLOCK + threadIdx.x;
+  if (row >= n) return;
+  double* a = A + row * lda + j;
+  double x[DN_NB];
+#pragma unroll
+  for (int k = 0; k < DN_NB; ++k) x[k] = a[k];
+#pragma unroll
+  for (int k = 0; k < DN_NB; ++k) {
+    double v = x[k];
+#pragma unroll
+    for (int m = 0; m < k; ++m) v = fma(-x[m], sL[k][m], v);
+    x[k] = v / sL[k][k];
+  }
+#pragma unroll
+  for (int k = 0; k < DN_NB; ++k) a[k] = x[k];
+}
+
+// A22 -= L21 L21^T below and right of a full diagonal block, the lower triangle only.  Workgroup
+// b of the 1-D grid takes tile (ty, tx) of the tiles with ty >= tx, rows first: b = ty (ty + 1) / 2
+// + tx.  As in dense_update_f64, 4 waves hold a 32 x 32 quarter each as 2 x 2 accumulators of
+// v_mfma_f64_16x16x4_f64 seeded with A22, 8 k-steps; here both operands are rows of L21, so both
+// LDS images are [row][k] with the stride DN_LS: -L21's rows of the tile's rows (A[row = lane & 15]
+// [k = lane >> 4]) and L21's rows of the tile's columns (B[k = lane >> 4][col = lane & 15]).
+// Rows past n: zeros in LDS, never stored.  Only entries with row >= column are seeded from and
+// stored to A; a quarter wholly above the diagonal (wave 1 of a diagonal tile) does nothing.
+__global__ __launch_bounds__(DN_BLOCK) void dense_potrf_update_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
+  __shared__ double sA[DN_TM][DN_LS];
+  __shared__ double sB[DN_TN][DN_LS];
+  const int t = threadIdx.x;
+  // (ty, tx) from b: the float root is within one of the answer, the two loops settle it
+  const unsigned b = blockIdx.x;
+  unsigned ty = (unsigned)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+  while ((dn_u64)ty * (ty + 1) / 2 > b) --ty;
+  while ((dn_u64)(ty + 1) * (ty + 2) / 2 <= b) ++ty;
+  const unsigned tx = b - (unsigned)((dn_u64)ty * (ty + 1) / 2);
+  const dn_u64 r0 = j + DN_NB + (dn_u64)ty * DN_TM;
+  const dn_u64 c0 = j + DN_NB + (dn_u64)tx * DN_TN;
+  for (int e = t; e < DN_TM * DN_NB; e += DN_BLOCK) {
+    const int r = e / DN_NB, k = e % DN_NB;
+    sA[r][k] = r0 + (dn_u64)r < n ? -A[(r0 + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
+    sB[r][k] = c0 + (dn_u64)r < n ? A[(c0 + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
+  }
+  __syncthreads();
+  const int lane = t & 63, w = t >> 6;
+  const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
+  if (ty == tx && wn > wm) return;  // (after the last barrier)
+  const int l15 = lane & 15, l4 = lane >> 4;
+  dn_f64x4 acc[2][2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
+        acc[mi][ni][q] = (r < n && c <= r) ? A[r * lda + c] : 0.0;
+      }
+#pragma unroll
+  for (int ks = 0; ks < DN_NB / 4; ++ks) {
+    double a[2], bv[2];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) a[mi] = sA[wm + mi * 16 + l15][ks * 4 + l4];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) bv[ni] = sB[wn + ni * 16 + l15][ks * 4 + l4];
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bv[ni], acc[mi][ni], 0, 0, 0);
+  }
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
+        if (r < n && c <= r) A[r * lda + c] = acc[mi][ni][q];
+      }
+}
+
+int launch_potrf(double* A, dn_u64 n, dn_u64 lda, int32_t* info, hipStream_t st) {
+  for (dn_u64 j = 0; j < n; j += DN_NB) {
+    const int nb = (int)(n - j < DN_NB ? n - j : DN_NB);
+    dense_potrf_diag_f64<<<1, DN_BLOCK, 0, st>>>(A, lda, j, nb, info);
+    if (j + nb < n) {  // rows below the block: the block is a full one
+      const dn_u64 rest = n - j - DN_NB;
+      dense_potrf_panel_f64<<<blocks_for(rest), DN_BLOCK, 0, st>>>(A, n, lda, j);
+      const dn_u64 tiles = (rest + DN_TM - 1) / DN_TM;  // <= 2^14: tiles (tiles + 1) / 2 fits a grid
+      dense_potrf_update_f64<<<(unsigned)(tiles * (tiles + 1) / 2), DN_BLOCK, 0, st>>>(A, n, lda, j);
+    }
+  }
+  return check_launch("fedagg_dense_potrf_f64");
+}
+
+}  // namespace
+
+extern "C" int fedagg_dense_potrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_info, void* stream) {
+  if (n == 0) return FEDAGG_DENSE_OK;
+  if (int rc = check_matrix(d_A, n, lda)) return rc;
+  if (!d_info) return fail(FEDAGG_DENSE_EINVAL, "d_info is NULL");
+  return launch_potrf(d_A, n, lda, d_info, (hipStream_t)stream);
+}

@@ -14,6 +14,11 @@ class IncompatibleAlgoStrategyError(Exception):
     """This algo is not compatible with this strategy."""
 
 
+class NegativeHessianMatrixError(Exception):
+    """The Hessian of a NewtonRaphson client has a negative eigenvalue: the problem is not convex,
+    or numerically unstable (the reference's exception of the same name)."""
+
+
 class LoadMetadataError(Exception):
     """metadata.json must name the ``model_file`` and ``function_file`` (exceptions.py:129-130)."""
 

@@ -20,6 +20,11 @@ everything of it -- constructor, ``name``, graph building (``build_compute_plan`
   partial pivoting, ``libfedagg_dense.so``), held to backward-error bounds instead of LAPACK's bits
   (include/fedagg_dense.h); the default is unchanged.
 
+The client half of NewtonRaphson ends every round with an eigenvalue check of its Hessian
+(torch_newton_raphson_algo.py:346-352); :func:`newton_raphson_hessian_check` restates it with an
+opt-in Cholesky certificate on the GPU ahead of it (``accelerate_algo(TorchNewtonRaphsonAlgo,
+hessian_check="device")`` or ``FEDAGG_NR_CHECK=device``).
+
 So the class goes straight into ``simulate_experiment`` / ``execute_experiment``::
 
     from substrafl.strategies import FedAvg
@@ -216,12 +221,74 @@ def newton_raphson_sums(shared_states, device: Optional[Devices] = None):
     return total_h, total_g
 
 
-def accelerate_algo(algo_cls, wire: bool = False):
+def _check_mode(check: str) -> str:
+    """``check`` (``"host"`` or ``"device"``) under the environment override ``FEDAGG_NR_CHECK``."""
+    mode = os.environ.get("FEDAGG_NR_CHECK") or check
+    if mode not in ("host", "device"):
+        raise ValueError(f"check must be 'host' or 'device', not {mode!r}")
+    return mode
+
+
+# the route the last newton_raphson_hessian_check of this process took ("route"), with the engine's
+# timing of the device part when it ran ("timing")
+last_hessian_check: dict = {}
+
+
+def newton_raphson_hessian_check(hessian, l2_coeff, device: Optional[Devices] = None, check: str = "device",
+                                 error_cls=None):
+    """The convexity check at the end of TorchNewtonRaphsonAlgo.train
+    (torch_newton_raphson_algo.py:346-352): raise ``error_cls`` (default
+    :class:`substrafl_amd.exceptions.NegativeHessianMatrixError`) unless every eigenvalue of
+    ``hessian`` is >= 0.  Returns the route taken, also left in ``last_hessian_check["route"]``.
+
+    ``check="host"``: the reference's lines as they are -- ``np.linalg.eig``, the real parts, the
+    message with the eigenvalue list and ``l2_coeff``.  Route ``"host"``.
+
+    ``check="device"``: a Cholesky factorisation on the GPU first
+    (:meth:`engine.AggregationEngine.hessian_cholesky_check`, ``fedagg_dense_potrf_f64``).  One that
+    runs to completion proves ``H + E`` positive definite for an ``E`` with ``|E| <=
+    gamma_{n+1} |L| |L^T|`` (include/fedagg_dense.h), and the Hessian is accepted: route
+    ``"device"``, no eigenvalue is computed.  A failed pivot (``info = j``: route ``"host after
+    device info=j"``) or a Hessian the engine declines (not float64, not square, not exactly
+    symmetric: the route is the engine's reason, ``"host: ..."``) proves nothing either way, and the
+    reference's host rule decides, raising with the reference's message.  The device therefore only
+    ever accepts; it never raises by itself.
+
+    The one divergence from the reference: a matrix whose smallest eigenvalue lies within the
+    factorisation's backward error below zero may be accepted on the device where ``dgeev`` reports
+    a negative eigenvalue -- a band in which ``dgeev``'s own sign is rounding noise as well.  No
+    shift or tolerance is applied.  ``FEDAGG_NR_CHECK=device|host`` overrides ``check``."""
+    mode = _check_mode(check)
+    route, timing = "host", None
+    if mode == "device":
+        eng = engine_for(device)
+        eng = eng._single() if hasattr(eng, "_single") else eng  # several GPUs: the first one
+        ok, info, reason = eng.hessian_cholesky_check(hessian)
+        timing = getattr(eng, "last_timing", None) if ok is not None else None
+        route = reason if ok is None else "device" if ok else f"host after device info={info}"
+        if isinstance(timing, dict):  # (an engine stand-in may keep no timing)
+            timing["check"] = route
+    last_hessian_check.clear()
+    last_hessian_check.update({"route": route, "timing": timing})
+    if route == "device":
+        return route
+    eigenvalues = np.linalg.eig(hessian)[0].real
+    if not (eigenvalues >= 0).all():
+        if error_cls is None:
+            from .exceptions import NegativeHessianMatrixError as error_cls
+        raise error_cls(
+            "Hessian matrix is not positive semi-definite, either the problem is not convex or due to numerical"
+            " instability. It is advised to try to increase the l2_coeff. "
+            f"Calculated eigenvalues are {eigenvalues.tolist()} and considered l2_coeff is {l2_coeff}")
+    return route
+
+
+def accelerate_algo(algo_cls, wire: bool = False, hessian_check: Optional[str] = None):
     """The client half: :func:`substrafl_amd.algorithms.accelerate.accelerate_algo`.
     Imported on call, so the aggregation side of this module never imports torch."""
     from .algorithms.accelerate import accelerate_algo as _accelerate_algo
 
-    return _accelerate_algo(algo_cls, wire=wire)
+    return _accelerate_algo(algo_cls, wire=wire, hessian_check=hessian_check)
 
 
 def scaffold_average(strategy, shared_states, aggregation_lr, device: Optional[Devices] = None, wire: bool = False):
