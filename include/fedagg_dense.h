@@ -21,8 +21,18 @@
  *     on the lower triangle (Higham thm 10.3: any summation order, with or without FMA; fp64
  *     sqrt and division are correctly rounded), so a run that ends with *d_info == 0 proves A + E
  *     positive definite for an E within that bound (tests/test_dense_potrf_gpu.py);
+ *   - the Householder LQ of fedagg_dense_gelqf_f64 / fedagg_dense_orglq_f64 (A = L Q, n <= m; LAPACK's
+ *     dgelqf + dorglq arithmetic with dlarfg's sign, beta = -sign(alpha) ||(alpha, x)||, so Q is
+ *     np.linalg.qr(A.T)[0].T with no sign fix-up): the relative residual ||A - L Q||_F / ||A||_2 and
+ *     the loss of orthogonality ||Q Q^T - I||_F are each at most m n u sqrt(n) (Higham thm 19.4 and
+ *     19.13 with constant 1: any summation order, with or without FMA) and at most
+ *     max(4 x LAPACK's own value, 8 u sqrt(n)) on the inputs of tests/test_dense_lq_gpu.py.  A
+ *     rank-deficient A still gives orthonormal rows (an all-zero row tail is tau = 0, H = I).
+ *     Norms are plain fp64 sums of squares: an A whose squares overflow or underflow fp64 is
+ *     outside the contract (a widened fp32 matrix never is);
  *   - results are deterministic: the same build gives the same bits on every run and stream
- *     (no atomics, every sum in a fixed order; contraction to FMA is allowed).
+ *     (no atomics, every sum in a fixed order -- for the LQ an order fixed by (n, m) alone;
+ *     contraction to FMA is allowed).
  * Inputs with NaN or Inf raise nothing and fault nothing; their outputs are unspecified.
  *
  * Conventions (those of fedagg.h)
@@ -94,6 +104,32 @@ int fedagg_dense_solve_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipi
  * whatever values there are (no fault): rows and columns [0, j) of L, the leading triangle, are
  * the factor's, everything else in the lower triangle is unspecified. */
 int fedagg_dense_potrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_info, void* stream);
+
+/* ---- Householder LQ of an n x m matrix, n <= m (added within ABI version 1) ----
+ * Here a matrix has n rows of m elements, lda >= m (ldq >= m); elements [m, lda) of a row are
+ * never read or written, and the launch sequence is a function of (n, m) alone.  n > m, n or m
+ * above FEDAGG_DENSE_MAX_N, lda < m, ldq < m and a NULL pointer (d_ws included: the workspace is
+ * never empty for n >= 1) are refused with FEDAGG_DENSE_EINVAL. */
+
+/* The blocking of the LQ kernels: `panel` rows are factored at a time, the block reflector works
+ * on tile_m x tile_n tiles, and W = C V^T is reduced over chunks of k_chunk columns. */
+int fedagg_dense_lq_blocking(int* panel, int* tile_m, int* tile_n, int* k_chunk);
+
+/* Bytes of device workspace either call below needs for an n x m matrix (0 for n == 0). */
+uint64_t fedagg_dense_lq_ws_bytes(uint64_t n, uint64_t m);
+
+/* A (n x m, n <= m, lda >= m) = L Q in place (blocked, right-looking, compact-WY block reflectors
+ * on v_mfma_f64_16x16x4_f64): L on and below the diagonal of the first n columns, reflector j,
+ * H_j = I - tau_j v_j^T v_j, in row j right of the diagonal (unit element implied), d_tau[j].  A row
+ * tail that is all zero gives tau_j = 0 and leaves a_jj as it is, sign included (always so for
+ * j = n - 1 when n == m). */
+int fedagg_dense_gelqf_f64(double* d_A, uint64_t n, uint64_t m, uint64_t lda, double* d_tau, void* d_ws, void* stream);
+
+/* The n x m Q with orthonormal rows (== np.linalg.qr(A.T)[0].T), from gelqf's output (d_A and d_tau
+ * are only read), into d_Q: the first n rows of the identity times H_k ... H_1, the block reflectors
+ * rebuilt from d_A and d_tau alone.  d_ws need not be the one gelqf used. */
+int fedagg_dense_orglq_f64(const double* d_A, uint64_t n, uint64_t m, uint64_t lda, const double* d_tau, double* d_Q,
+                           uint64_t ldq, void* d_ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,10 @@ SIGNATURES = {
     "fedagg_dense_getrs_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void, c_void]),
     "fedagg_dense_solve_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void, c_void, c_void, c_void]),
     "fedagg_dense_potrf_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void]),
+    "fedagg_dense_lq_blocking": (c_int, [P(c_int), P(c_int), P(c_int), P(c_int)]),
+    "fedagg_dense_lq_ws_bytes": (c_u64, [c_u64, c_u64]),
+    "fedagg_dense_gelqf_f64": (c_int, [c_void, c_u64, c_u64, c_u64, c_void, c_void, c_void]),
+    "fedagg_dense_orglq_f64": (c_int, [c_void, c_u64, c_u64, c_u64, c_void, c_void, c_u64, c_void, c_void]),
 }
 
 ABI_VERSION = 1
@@ -80,3 +84,11 @@ def blocking() -> tuple:
     a, b, c = c_int(), c_int(), c_int()
     check(load().fedagg_dense_blocking(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "dense_blocking")
     return a.value, b.value, c.value
+
+
+def lq_blocking() -> tuple:
+    """``(panel, tile_m, tile_n, k_chunk)`` of the LQ kernels (``fedagg_dense_lq_blocking``)."""
+    a, b, c, d = c_int(), c_int(), c_int(), c_int()
+    check(load().fedagg_dense_lq_blocking(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d)),
+          "dense_lq_blocking")
+    return a.value, b.value, c.value, d.value

@@ -1243,6 +1243,68 @@ class AggregationEngine:
                             "fetch_s": t3 - t2, "total_s": t3 - t0}
         return int(info[0]) == 0, int(info[0]), "device"
 
+    @serialized
+    def orthonormal_rows(self, a):
+        """The orthonormalisation of one layer of FedPCA's averaged state (opt-in; fed_pca.py:289-299,
+        ``np.linalg.qr(a.T)[0].T``) on the device: ``a`` (``n x m``, ``n <= m``) copied into a session
+        buffer, widened to fp64 by ``fedagg_cast`` when it is fp32 (NumPy factors an fp32 matrix in
+        fp64 too and rounds the result), ``fedagg_dense_gelqf_f64`` then ``fedagg_dense_orglq_f64``
+        (include/fedagg_dense.h: blocked Householder LQ with LAPACK's sign convention, held to error
+        bounds, not to LAPACK's bits) on the session stream, ``Q`` narrowed back for fp32 and
+        fetched.  The host array is only read.
+
+        Returns ``(q, "device")``, ``q`` a C-contiguous ``n x m`` array of ``a``'s dtype with
+        orthonormal rows; or ``(None, "host: ...")``, and nothing has run, unless ``a`` is a 2-D
+        native-byte-order float32 / float64 ``ndarray`` with ``1 <= n <= m``.  ``last_timing``:
+        ``stage_s``, ``factor_ms``, ``fetch_s``, ``total_s``, ``n``, ``m``, ``qr``."""
+        if not isinstance(a, np.ndarray):
+            return None, f"host: not an ndarray ({type(a).__name__})"
+        if a.dtype.kind != "f" or a.dtype.itemsize not in (4, 8):
+            return None, f"host: dtype {a.dtype} is not float32 or float64"
+        if not a.dtype.isnative:
+            return None, f"host: not in native byte order ({a.dtype.str})"
+        if a.ndim != 2:
+            return None, f"host: shape {a.shape} is not a 2-D matrix"
+        n, m = (int(v) for v in a.shape)
+        if n < 1:
+            return None, f"host: empty matrix {a.shape}"
+        if n > m:
+            return None, f"host: shape {a.shape} has more rows than columns (n > m)"
+        from . import _native_dense
+
+        lib = _native_dense.load()
+        s = self.session()
+        t0 = time.perf_counter()
+        wide = a.dtype == np.float64
+        d_a = s.buffer(self._B_OUT, n * m * 8)
+        d_q = s.buffer(self._B_COUT, n * m * 8)
+        d_tau = s.buffer(self._B_CNT, n * 8)
+        d_ws = s.buffer(self._B_WS, int(lib.fedagg_dense_lq_ws_bytes(n, m)))
+        d_narrow = d_a if wide else s.buffer(self._B_TMP, n * m * 4)
+        s.stage(d_narrow, n * m * a.dtype.itemsize, [[np.ascontiguousarray(a)]])
+        t1 = time.perf_counter()
+        ev = self._EV_NR
+        s.event_record(ev[0])
+        if not wide:
+            s.cast(d_narrow, np.float32, d_a, np.float64, n * m)  # exact
+        for d in (d_a, d_q, d_tau, d_ws):
+            s._bump(d)
+        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
+        _native_dense.check(lib.fedagg_dense_gelqf_f64(vp(d_a), n, m, m, vp(d_tau), vp(d_ws), st), "dense_gelqf_f64")
+        _native_dense.check(lib.fedagg_dense_orglq_f64(vp(d_a), n, m, m, vp(d_tau), vp(d_q), m, vp(d_ws), st),
+                            "dense_orglq_f64")
+        if not wide:
+            s.cast(d_q, np.float64, d_narrow, np.float32, n * m)  # NumPy's astype rounding
+        s.event_record(ev[1])
+        s.sync()  # so that fetch_s below is the fetch alone, not the wait for the kernels
+        t2 = time.perf_counter()
+        q = np.empty((n, m), a.dtype)
+        s.fetch(d_q if wide else d_narrow, q)
+        t3 = time.perf_counter()
+        self.last_timing = {"qr": "device", "n": n, "m": m, "stage_s": t1 - t0,
+                            "factor_ms": s.event_elapsed_ms(ev[0], ev[1]), "fetch_s": t3 - t2, "total_s": t3 - t0}
+        return q, "device"
+
     @staticmethod
     def _chain(s, kind: str, ptrs: List[int], coeffs: List[float], M: int, d_acc: int) -> None:
         """acc = fl(acc + fl(x_i * fl_kind(c_i))) over the rows ``ptrs`` in order, on the session

@@ -12,7 +12,9 @@ everything of it -- constructor, ``name``, graph building (``build_compute_plan`
   and ``aggregation_lr`` after the sum, with the ``c`` equality check of scaffold.py:193-196
   counted while ``c`` is staged;
 * ``FedPCA.avg_shared_states`` / ``avg_shared_states_with_qr`` (fed_pca.py:210-299): FedAvg's
-  reduction (+ the reference's ``np.linalg.qr`` of each averaged matrix);
+  reduction (+ the reference's ``np.linalg.qr`` of each averaged matrix; opt-in,
+  ``accelerate(FedPCA, qr="device")`` or ``FEDAGG_PCA_QR=device``: an fp64 Householder LQ on the GPU
+  instead, held to error bounds, DESIGN.md);
 * ``NewtonRaphson.compute_averaged_states`` (newton_raphson.py:151-216): the weighted sums of the
   clients' Hessians and gradients (the explicit ``+=`` chain, ``engine.sequential_sum``), then the
   reference's own ``np.linalg.solve`` and unflatten on the host.  Opt-in, ``accelerate(NewtonRaphson,
@@ -51,6 +53,7 @@ import numpy as np
 from . import handoff
 from .engine import Devices, engine_for
 from .strategies.fed_avg import check_same_shapes, weighted_average
+from .strategies.fed_pca import orthonormal_layers
 from .strategies.scaffold import Scaffold as _MirrorScaffold
 from .strategies.strategy import Strategy as _MirrorStrategy
 
@@ -73,16 +76,21 @@ def _solve_mode(solve: str) -> str:
     return mode
 
 
-def accelerate(strategy_cls, device: Devices = None, solve: str = "host"):
+def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host"):
     """A subclass of the reference strategy class ``strategy_cls`` (``FedAvg``, ``Scaffold``,
     ``FedPCA``, ``NewtonRaphson`` or a subclass of one of them) whose aggregation methods run on the
     engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
     "all").  ``solve`` matters for NewtonRaphson only: ``"host"`` (the default) keeps the
     reference's ``np.linalg.solve``, bit for bit; ``"device"`` solves the Newton system on the GPU
     as well (:func:`newton_raphson_update`).  ``FEDAGG_NR_SOLVE=device|host`` overrides it, read
-    when the aggregation runs."""
+    when the aggregation runs.  ``qr`` matters for FedPCA only: ``"host"`` (the default) keeps the
+    reference's ``np.linalg.qr`` of each averaged matrix, bit for bit; ``"device"`` orthonormalises
+    each one on the GPU (:func:`strategies.fed_pca.orthonormal_layers`).  ``FEDAGG_PCA_QR=device|host``
+    overrides it, read when the aggregation runs."""
     if solve not in ("host", "device"):
         raise ValueError(f"solve must be 'host' or 'device', not {solve!r}")
+    if qr not in ("host", "device"):
+        raise ValueError(f"qr must be 'host' or 'device', not {qr!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
     empty = exceptions.EmptySharedStatesError
     base_init = strategy_cls.__init__
@@ -118,11 +126,13 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host"):
             return averaged_cls(avg_parameters_update=out)
 
         def avg_shared_states_with_qr(self, shared_states):
-            """fed_pca.py:261-299: the average on the engine, then the reference's QR per layer."""
+            """fed_pca.py:261-299: the average on the engine, then the reference's QR per layer
+            (``qr="host"``) or the fp64 Householder LQ on the device (``qr="device"``)."""
             out = weighted_average(shared_states, "FedPCASharedState", self._fedagg_device, wire=False,
                                    empty_error=empty)
-            return averaged_cls(avg_parameters_update=[np.linalg.qr(a.T)[0].T for a in out])
+            return averaged_cls(avg_parameters_update=orthonormal_layers(out, self._fedagg_device, self._fedagg_qr))
 
+        ns["_fedagg_qr"] = qr
         ns["avg_shared_states"] = remote(avg_shared_states)
         ns["avg_shared_states_with_qr"] = remote(avg_shared_states_with_qr)
         ns["_aggregation_methods"] = {"avg_shared_states": "fedavg", "avg_shared_states_with_qr": "fedavg"}
