@@ -5,22 +5,22 @@
 //                      panel, scale, rank-1 updates),
 //   dense_laswp_f64    the panel's row interchanges on the columns left and right of it,
 //   dense_trsm_f64     U12 = L11^-1 A12 (one thread per column, L11 from LDS),
-//   dense_update_f64   A22 -= L21 U12 on v_mfma_f64_16x16x4_f64, DN_TM x DN_TN tiles through LDS,
+//   dense_update_f64   A22 -= L21 U12, DN_TM x DN_TN tiles (the tile step of dense_internal.h),
 // then dense_perm_f64 / dense_fwd_f64 / dense_bwd_f64 for the right-hand side.  The stream orders
 // the kernels; no kernel waits on another workgroup, and no sum uses an atomic.
 #include "dense_internal.h"
 
-// (DN_NB, DN_TM, DN_TN and DN_BLOCK are dense_internal.h's, stated again here, where the tests of
-// the panel's strides read them; a difference is the compiler's "macro redefined")
-#define DN_NB 32               // panel width; block of the triangular solves and substitutions
-#define DN_TM 64               // trailing-update tile, rows
-#define DN_TN 64               // trailing-update tile, columns
-#define DN_PANEL_THREADS 512   // the panel kernel's one workgroup: DN_NB columns x DN_RG row groups
+// The panel kernel's blocking.  DN_NB is dense_internal.h's: the strides below are multiples of it, and the suite
+// reads all four from this file, so it is stated here once more; a value other than the header's does not compile.
+#pragma clang diagnostic push
+#pragma clang diagnostic error "-Wmacro-redefined"
+#define DN_NB 32
+#pragma clang diagnostic pop
+#define DN_PANEL_THREADS 512  // the panel kernel's one workgroup: DN_NB columns x DN_RG row groups
 #define DN_RG (DN_PANEL_THREADS / 32)
-#define DN_BLOCK 256
 #define DN_UB 8                // rows a panel thread keeps in flight per step of the rank-1 update
 
-using namespace fedagg_dense_detail;  // g_error, fail, check_launch, check_matrix, blocks_for
+using namespace fedagg_dense_detail;
 
 namespace {
 
@@ -170,10 +170,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_laswp_f64(double* A, dn_u64 n,
 // DN_NB values in registers, the unit lower triangle L11 broadcast from LDS.
 __global__ __launch_bounds__(DN_BLOCK) void dense_trsm_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
   __shared__ double sL[DN_NB][DN_NB + 1];
-  for (int e = threadIdx.x; e < DN_NB * DN_NB; e += DN_BLOCK) {
-    const int r = e / DN_NB, k = e % DN_NB;
-    sL[r][k] = k < r ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
-  }
+  load_diag_block(sL, A, lda, j, threadIdx.x, [](int r, int k) { return k < r; });
   __syncthreads();
   const dn_u64 col = j + DN_NB + (dn_u64)blockIdx.x * DN_BLOCK + threadIdx.x;
   if (col >= n) return;
@@ -191,14 +188,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_trsm_f64(double* A, dn_u64 n, 
   for (int r = 1; r < DN_NB; ++r) A[(j + (dn_u64)r) * lda + col] = x[r];
 }
 
-// A22 -= L21 U12 below and right of a full panel.  A workgroup of 4 waves takes a DN_TM x DN_TN
-// tile of A22: -L21's 64 x 32 and U12's 32 x 64 pieces go through LDS, each wave holds a 32 x 32
-// quarter as 2 x 2 accumulators of v_mfma_f64_16x16x4_f64, seeded with A22 itself, 8 k-steps.
-// Operand maps of that instruction: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col =
-// lane & 15], C/D register q of a lane: row (lane >> 4) + 4 q, column lane & 15.
-// Rows and columns past n: zeros in LDS, their accumulator entries never stored.
-#define DN_LS (DN_NB + 4)   // sL row stride: 4 (mod 32) doubles, the 64 operand reads 2 per bank
-#define DN_US (DN_TN + 16)  // sU row stride: 16 (mod 32) doubles, likewise
+// A22 -= L21 U12 below and right of a full panel.  A workgroup takes a DN_TM x DN_TN tile of A22:
+// -L21's 64 x 32 and U12's 32 x 64 pieces go through LDS, each wave holds a 32 x 32 quarter seeded
+// with A22 itself.  Rows and columns past n: zeros in LDS, their accumulator entries never stored.
 __global__ __launch_bounds__(DN_BLOCK) void dense_update_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
   __shared__ double sL[DN_TM][DN_LS];
   __shared__ double sU[DN_NB][DN_US];
@@ -214,41 +206,17 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_update_f64(double* A, dn_u64 n
     sU[k][c] = c0 + (dn_u64)c < n ? A[(j + (dn_u64)k) * lda + c0 + (dn_u64)c] : 0.0;
   }
   __syncthreads();
-  const int lane = t & 63, w = t >> 6;
-  const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-  const int l15 = lane & 15, l4 = lane >> 4;
+  const TileLane ln = quarter_lane(t);
   dn_f64x4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        acc[mi][ni][q] = (r < n && c < n) ? A[r * lda + c] : 0.0;
-      }
-#pragma unroll
-  for (int ks = 0; ks < DN_NB / 4; ++ks) {
-    double a[2], b[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) a[mi] = sL[wm + mi * 16 + l15][ks * 4 + l4];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) b[ni] = sU[ks * 4 + l4][wn + ni * 16 + l15];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 r = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    acc[mi][ni][q] = (r < n && c < n) ? A[r * lda + c] : 0.0;
   }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        if (r < n && c < n) A[r * lda + c] = acc[mi][ni][q];
-      }
+  tile_step(acc, ln, sL, [&](int k, int c) { return sU[k][c]; });
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 r = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    if (r < n && c < n) A[r * lda + c] = acc[mi][ni][q];
+  }
 }
 
 // b <- P b: the interchanges in order, by one thread (each may depend on the one before).
@@ -273,15 +241,11 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_fwd_f64(const double* LU, dn_u
   __shared__ double sx[DN_NB];
   __shared__ double sT[DN_NB][DN_NB + 1];
   const int t = threadIdx.x;
-  const int bs = (int)(n - jb < DN_NB ? n - jb : DN_NB);
+  const int bs = panel_width(n, jb);
   const bool has_prev = jb > 0;
   const dn_u64 prev = jb - DN_NB;
   if (has_prev && t < DN_NB) sx[t] = b[prev + (dn_u64)t];
-  if (blockIdx.x == 0)
-    for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
-      const int r = e / DN_NB, k = e % DN_NB;
-      sT[r][k] = (k < r && r < bs) ? LU[(jb + (dn_u64)r) * lda + jb + (dn_u64)k] : 0.0;
-    }
+  if (blockIdx.x == 0) load_diag_block(sT, LU, lda, jb, t, [bs](int r, int k) { return k < r && r < bs; });
   __syncthreads();
   const dn_u64 i = jb + (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
   double ri = 0.0;
@@ -310,16 +274,12 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_bwd_f64(const double* LU, dn_u
   __shared__ double sx[DN_NB];
   __shared__ double sT[DN_NB][DN_NB + 1];
   const int t = threadIdx.x;
-  const int bs = (int)(n - jb < DN_NB ? n - jb : DN_NB);
+  const int bs = panel_width(n, jb);
   const dn_u64 prev = jb + DN_NB;
   const bool has_prev = prev < n;
-  const int pbs = has_prev ? (int)(n - prev < DN_NB ? n - prev : DN_NB) : 0;
+  const int pbs = has_prev ? panel_width(n, prev) : 0;
   if (t < DN_NB) sx[t] = t < pbs ? b[prev + (dn_u64)t] : 0.0;
-  if (blockIdx.x == 0)
-    for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
-      const int r = e / DN_NB, k = e % DN_NB;
-      sT[r][k] = (k >= r && k < bs) ? LU[(jb + (dn_u64)r) * lda + jb + (dn_u64)k] : 0.0;
-    }
+  if (blockIdx.x == 0) load_diag_block(sT, LU, lda, jb, t, [bs](int r, int k) { return k >= r && k < bs; });
   __syncthreads();
   const dn_u64 top = jb + (dn_u64)bs - 1;
   const dn_u64 q = (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
@@ -346,7 +306,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_bwd_f64(const double* LU, dn_u
 
 int launch_getrf(double* A, dn_u64 n, dn_u64 lda, int32_t* ipiv, int32_t* info, hipStream_t st) {
   for (dn_u64 j = 0; j < n; j += DN_NB) {
-    const int nb = (int)(n - j < DN_NB ? n - j : DN_NB);
+    const int nb = panel_width(n, j);
     dense_panel_f64<<<1, DN_PANEL_THREADS, 0, st>>>(A, n, lda, j, nb, ipiv, info);
     if (n > (dn_u64)nb) dense_laswp_f64<<<blocks_for(n - nb), DN_BLOCK, 0, st>>>(A, n, lda, j, nb, ipiv);
     if (j + nb < n) {  // a trailing matrix: the panel is a full one
@@ -363,8 +323,7 @@ int launch_getrs(const double* LU, dn_u64 n, dn_u64 lda, const int32_t* ipiv, do
   dense_perm_f64<<<1, 64, 0, st>>>(ipiv, n, b);
   for (dn_u64 jb = 0; jb < n; jb += DN_NB) dense_fwd_f64<<<blocks_for(n - jb), DN_BLOCK, 0, st>>>(LU, n, lda, b, jb);
   for (dn_u64 jb = (n - 1) / DN_NB * DN_NB;; jb -= DN_NB) {
-    const dn_u64 bs = n - jb < DN_NB ? n - jb : DN_NB;
-    dense_bwd_f64<<<blocks_for(jb + bs), DN_BLOCK, 0, st>>>(LU, n, lda, b, jb);
+    dense_bwd_f64<<<blocks_for(jb + (dn_u64)panel_width(n, jb)), DN_BLOCK, 0, st>>>(LU, n, lda, b, jb);
     if (jb == 0) break;
   }
   return check_launch("fedagg_dense_getrs_f64");

@@ -5,12 +5,13 @@
 // factorisation with compact-WY block reflectors, H_1 .. H_nb = I - V^T T V: per panel of DN_NB rows
 //   dense_lq_panel_f64   one workgroup factors rows [j, j + nb), columns [j, m) in global memory
 //                        (dlarfg's rule per row, then a dot product and an axpy per remaining row),
-//   dense_lq_wpart_f64   W = C V^T on v_mfma_f64_16x16x4_f64, one workgroup per (DN_TM rows,
-//                        LQ_KC columns): partial products into the workspace; with C = V itself
-//                        the same kernel gives the partials of V V^T,
+//   dense_lq_wpart_f64   W = C V^T, one workgroup per (DN_TM rows, LQ_KC columns): partial products
+//                        into the workspace; with C = V itself the same kernel gives the partials
+//                        of V V^T,
 //   dense_lq_t_f64       V V^T summed in chunk order, then T (upper triangular) from it and tau,
 //   dense_lq_wt_f64      W summed in chunk order and multiplied by T (T^T for orglq),
-//   dense_lq_apply_f64   C -= (W T) V on DN_TM x DN_TN tiles, the shape of dense_update_f64.
+//   dense_lq_apply_f64   C -= (W T) V on DN_TM x DN_TN tiles
+// (both products are the tile step of dense_internal.h).
 // orglq starts from the first n rows of the identity (dense_lq_eye_f64) and applies the block
 // reflectors in reverse order with T^T, T rebuilt from V and tau.  The stream orders the kernels;
 // no kernel waits on another workgroup, no sum uses an atomic, every sum runs in an order fixed
@@ -20,7 +21,6 @@
 #define LQ_KC 512                  // columns one workgroup of dense_lq_wpart_f64 reduces over
 #define LQ_PANEL_THREADS 1024      // the panel kernel's one workgroup
 #define LQ_PW (LQ_PANEL_THREADS / 64)
-#define LQ_US (DN_TN + 16)         // sU row stride: 16 (mod 32) doubles, the 64 operand reads 2 per bank
 
 static_assert(LQ_KC % DN_NB == 0, "a chunk is a whole number of 32-column steps");
 
@@ -106,11 +106,9 @@ __global__ __launch_bounds__(LQ_PANEL_THREADS) void dense_lq_panel_f64(double* A
 
 // part[chunk][lr][0 .. 32) = sum over the chunk's columns of C[crow0 + lr][c] V[i][c], lr in
 // [0, nrows): workgroup (chunk, row tile) walks columns [j + chunk LQ_KC, + LQ_KC) below m in steps
-// of 32, both operands through LDS as [row][k] with the stride DN_LS (the maps of
-// dense_potrf_update_f64: A[row = lane & 15][k = lane >> 4], B[k = lane >> 4][col = lane & 15]);
-// wave w holds rows 16 w .. 16 w + 15 of the tile as two accumulators.  c_is_v: C is V itself
-// (nrows = nb), so the result is the chunk's share of V V^T.  Rows past nrows and columns past m:
-// zeros in LDS, never stored.
+// of 32, both operands through LDS as [row][k]; wave w holds rows 16 w .. 16 w + 15 of the tile as
+// two accumulators.  c_is_v: C is V itself (nrows = nb), so the result is the chunk's share of
+// V V^T.  Rows past nrows and columns past m: zeros in LDS, never stored.
 __global__ __launch_bounds__(DN_BLOCK) void dense_lq_wpart_f64(const double* C, dn_u64 ldc, dn_u64 crow0, dn_u64 nrows,
                                                                int c_is_v, const double* A, dn_u64 lda, dn_u64 j, int nb,
                                                                dn_u64 m, double* part) {
@@ -121,13 +119,9 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_lq_wpart_f64(const double* C, 
   const dn_u64 r0 = (dn_u64)blockIdx.y * DN_TM;
   const dn_u64 k0 = j + chunk * LQ_KC;
   const dn_u64 k1 = k0 + LQ_KC < m ? k0 + LQ_KC : m;
-  const int lane = t & 63, w = t >> 6;
-  const int l15 = lane & 15, l4 = lane >> 4;
-  dn_f64x4 acc[2];
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[ni][q] = 0.0;
+  const TileLane ln = strip_lane(t);
+  dn_f64x4 acc[1][2];
+  DN_EACH_ACC(1, 2) acc[mi][ni][q] = 0.0;
   for (dn_u64 kk = k0; kk < k1; kk += DN_NB) {
     for (int e = t; e < DN_TM * DN_NB; e += DN_BLOCK) {
       const int r = e / DN_NB, k = e % DN_NB;
@@ -142,22 +136,13 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_lq_wpart_f64(const double* C, 
       sV[i][k] = c < k1 ? lq_v(A, lda, j, nb, i, c, m) : 0.0;
     }
     __syncthreads();
-#pragma unroll
-    for (int ks = 0; ks < DN_NB / 4; ++ks) {
-      const double a = sC[w * 16 + l15][ks * 4 + l4];
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, sV[ni * 16 + l15][ks * 4 + l4], acc[ni], 0, 0, 0);
-    }
+    tile_step(acc, ln, sC, [&](int k, int i) { return sV[i][k]; });
     __syncthreads();
   }
-#pragma unroll
-  for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const dn_u64 lr = r0 + (dn_u64)(w * 16 + l4 + 4 * q);
-      if (lr < nrows) part[(chunk * nrows + lr) * DN_NB + (dn_u64)(ni * 16 + l15)] = acc[ni][q];
-    }
+  DN_EACH_ACC(1, 2) {
+    const dn_u64 lr = r0 + (dn_u64)ln.row(mi, q);
+    if (lr < nrows) part[(chunk * nrows + lr) * DN_NB + (dn_u64)ln.col(ni)] = acc[mi][ni][q];
+  }
 }
 
 // T of the block (DN_NB x DN_NB, upper triangular, zeros past nb) from G = V V^T -- its nch partials
@@ -168,14 +153,13 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_lq_t_f64(const double* part, u
   __shared__ double sG[DN_NB][DN_NB + 1];
   __shared__ double sT[DN_NB][DN_NB + 1];
   const int t = threadIdx.x;
-  for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
-    const int i = e / DN_NB, k = e % DN_NB;
+  each_block_elem(t, [&](int i, int k) {
     double g = 0.0;
     if (i < nb && k < nb)
       for (unsigned ch = 0; ch < nch; ++ch) g += part[((dn_u64)ch * (dn_u64)nb + (dn_u64)i) * DN_NB + (dn_u64)k];
     sG[i][k] = g;
     sT[i][k] = 0.0;
-  }
+  });
   __syncthreads();
   for (int k = 0; k < nb; ++k) {
     const double tk = tau[k];
@@ -218,15 +202,15 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_lq_wt_f64(const double* part, 
   if (r < nrows) W2[r * DN_NB + (dn_u64)k] = o;
 }
 
-// C -= W2 V on rows [crow0, crow0 + nrows), columns [j, m).  As dense_update_f64: 4 waves take a
-// DN_TM x DN_TN tile, -W2's 64 x 32 and V's 32 x 64 pieces go through LDS (V with its unit diagonal
-// and the zeros left of it), each wave holds a 32 x 32 quarter as 2 x 2 accumulators seeded with C
-// itself, 8 k-steps.  Rows past nrows and columns past m: zeros in LDS, never loaded or stored.
+// C -= W2 V on rows [crow0, crow0 + nrows), columns [j, m).  A workgroup takes a DN_TM x DN_TN tile:
+// -W2's 64 x 32 and V's 32 x 64 pieces go through LDS (V with its unit diagonal and the zeros left
+// of it), each wave holds a 32 x 32 quarter seeded with C itself.  Rows past nrows and columns past
+// m: zeros in LDS, never loaded or stored.
 __global__ __launch_bounds__(DN_BLOCK) void dense_lq_apply_f64(double* C, dn_u64 ldc, dn_u64 crow0, dn_u64 nrows,
                                                                const double* W2, const double* A, dn_u64 lda, dn_u64 j,
                                                                int nb, dn_u64 m) {
   __shared__ double sL[DN_TM][DN_LS];
-  __shared__ double sU[DN_NB][LQ_US];
+  __shared__ double sU[DN_NB][DN_US];
   const int t = threadIdx.x;
   const dn_u64 r0 = (dn_u64)blockIdx.y * DN_TM;
   const dn_u64 c0 = j + (dn_u64)blockIdx.x * DN_TN;
@@ -239,41 +223,17 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_lq_apply_f64(double* C, dn_u64
     sU[k][c] = lq_v(A, lda, j, nb, k, c0 + (dn_u64)c, m);
   }
   __syncthreads();
-  const int lane = t & 63, w = t >> 6;
-  const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-  const int l15 = lane & 15, l4 = lane >> 4;
+  const TileLane ln = quarter_lane(t);
   dn_f64x4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 lr = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        acc[mi][ni][q] = (lr < nrows && c < m) ? C[(crow0 + lr) * ldc + c] : 0.0;
-      }
-#pragma unroll
-  for (int ks = 0; ks < DN_NB / 4; ++ks) {
-    double a[2], b[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) a[mi] = sL[wm + mi * 16 + l15][ks * 4 + l4];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) b[ni] = sU[ks * 4 + l4][wn + ni * 16 + l15];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 lr = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    acc[mi][ni][q] = (lr < nrows && c < m) ? C[(crow0 + lr) * ldc + c] : 0.0;
   }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 lr = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        if (lr < nrows && c < m) C[(crow0 + lr) * ldc + c] = acc[mi][ni][q];
-      }
+  tile_step(acc, ln, sL, [&](int k, int c) { return sU[k][c]; });
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 lr = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    if (lr < nrows && c < m) C[(crow0 + lr) * ldc + c] = acc[mi][ni][q];
+  }
 }
 
 // Q = the first n rows of the m x m identity (columns [0, m) of every row; [m, ldq) untouched).
@@ -307,7 +267,7 @@ void launch_block(double* C, dn_u64 ldc, dn_u64 crow0, dn_u64 nrows, const doubl
 
 int launch_gelqf(double* A, dn_u64 n, dn_u64 m, dn_u64 lda, double* tau, double* ws, hipStream_t st) {
   for (dn_u64 j = 0; j < n; j += DN_NB) {
-    const int nb = (int)(n - j < DN_NB ? n - j : DN_NB);
+    const int nb = panel_width(n, j);
     dense_lq_panel_f64<<<1, LQ_PANEL_THREADS, 0, st>>>(A, m, lda, j, nb, tau);
     if (j + nb < n)  // rows below the panel: the panel is a full one
       launch_block(A, lda, j + DN_NB, n - j - DN_NB, A, lda, n, m, j, nb, tau, 0, ws, st);
@@ -319,7 +279,7 @@ int launch_orglq(const double* A, dn_u64 n, dn_u64 m, dn_u64 lda, const double* 
                  hipStream_t st) {
   dense_lq_eye_f64<<<dim3(blocks_for(m), (unsigned)(n < 4096 ? n : 4096)), DN_BLOCK, 0, st>>>(Q, n, m, ldq);
   for (dn_u64 j = (n - 1) / DN_NB * DN_NB;; j -= DN_NB) {
-    const int nb = (int)(n - j < DN_NB ? n - j : DN_NB);
+    const int nb = panel_width(n, j);
     launch_block(Q, ldq, j, n - j, A, lda, n, m, j, nb, tau, 1, ws, st);
     if (j == 0) break;
   }
@@ -329,11 +289,10 @@ int launch_orglq(const double* A, dn_u64 n, dn_u64 m, dn_u64 lda, const double* 
 // The argument checks of both entry points (n >= 1 here), before any HIP call.
 int check_lq(const void* d_A, dn_u64 n, dn_u64 m, dn_u64 lda, const void* d_tau, const void* d_ws) {
   if (!d_A) return fail(FEDAGG_DENSE_EINVAL, "d_A is NULL");
-  if (n > FEDAGG_DENSE_MAX_N) return fail(FEDAGG_DENSE_EINVAL, "n = %lld exceeds FEDAGG_DENSE_MAX_N", (long long)n);
-  if (m > FEDAGG_DENSE_MAX_N) return fail(FEDAGG_DENSE_EINVAL, "m = %lld exceeds FEDAGG_DENSE_MAX_N", (long long)m);
+  if (int rc = check_dim("n", n)) return rc;
+  if (int rc = check_dim("m", m)) return rc;
   if (n > m) return fail(FEDAGG_DENSE_EINVAL, "n = %lld is larger than m (the LQ takes n <= m)", (long long)n);
-  if (lda < m) return fail(FEDAGG_DENSE_EINVAL, "lda = %lld is smaller than m", (long long)lda);
-  if (lda > UINT64_MAX / 8 / n) return fail(FEDAGG_DENSE_EINVAL, "n * lda * 8 overflows 64 bits (n = %lld)", (long long)n);
+  if (int rc = check_ld("lda", lda, "m", m, n)) return rc;
   if (!d_tau) return fail(FEDAGG_DENSE_EINVAL, "d_tau is NULL");
   if (!d_ws) return fail(FEDAGG_DENSE_EINVAL, "d_ws is NULL (fedagg_dense_lq_ws_bytes(n, m) > 0)");
   return FEDAGG_DENSE_OK;
@@ -369,8 +328,7 @@ int fedagg_dense_orglq_f64(const double* d_A, uint64_t n, uint64_t m, uint64_t l
   if (n == 0) return FEDAGG_DENSE_OK;
   if (!d_Q) return fail(FEDAGG_DENSE_EINVAL, "d_Q is NULL");
   if (int rc = check_lq(d_A, n, m, lda, d_tau, d_ws)) return rc;
-  if (ldq < m) return fail(FEDAGG_DENSE_EINVAL, "ldq = %lld is smaller than m", (long long)ldq);
-  if (ldq > UINT64_MAX / 8 / n) return fail(FEDAGG_DENSE_EINVAL, "n * ldq * 8 overflows 64 bits (n = %lld)", (long long)n);
+  if (int rc = check_ld("ldq", ldq, "m", m, n)) return rc;
   return launch_orglq(d_A, n, m, lda, d_tau, d_Q, ldq, (double*)d_ws, (hipStream_t)stream);
 }
 

@@ -5,8 +5,8 @@
 //   dense_potrf_diag_f64    one workgroup factors the diagonal block in LDS and records the first
 //                           pivot that is not > 0,
 //   dense_potrf_panel_f64   L21 = A21 L11^-T (one thread per row, L11 from LDS),
-//   dense_potrf_update_f64  A22 -= L21 L21^T on v_mfma_f64_16x16x4_f64, the DN_TM x DN_TN tiles on
-//                           and below the diagonal only, both operands through LDS.
+//   dense_potrf_update_f64  A22 -= L21 L21^T, the DN_TM x DN_TN tiles on and below the diagonal
+//                           only (the tile step of dense_internal.h).
 // The stream orders the kernels; no kernel waits on another workgroup, no sum uses an atomic, and
 // no index or trip count depends on a matrix value: after a failed pivot everything still runs,
 // on whatever values (NaN) there are.
@@ -29,10 +29,7 @@ namespace {
 __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_diag_f64(double* A, dn_u64 lda, dn_u64 j, int nb, int32_t* info) {
   __shared__ double s[DN_NB][DN_NB + 1];
   const int t = threadIdx.x;
-  for (int e = t; e < DN_NB * DN_NB; e += DN_BLOCK) {
-    const int r = e / DN_NB, k = e % DN_NB;
-    s[r][k] = (k <= r && r < nb) ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
-  }
+  load_diag_block(s, A, lda, j, t, [nb](int r, int k) { return k <= r && r < nb; });
   __syncthreads();
   int32_t first = 0;  // thread 0's: 1-based index of the block's first failed pivot
   for (int c = 0; c < nb; ++c) {
@@ -66,10 +63,7 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_diag_f64(double* A, dn_u
 // the row is (a_ik - sum_{m<k} l_im l_km) / l_kk, m ascending.
 __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_panel_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
   __shared__ double sL[DN_NB][DN_NB + 1];
-  for (int e = threadIdx.x; e < DN_NB * DN_NB; e += DN_BLOCK) {
-    const int r = e / DN_NB, k = e % DN_NB;
-    sL[r][k] = k <= r ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
-  }
+  load_diag_block(sL, A, lda, j, threadIdx.x, [](int r, int k) { return k <= r; });
   __syncthreads();
   const dn_u64 row = j + DN_NB + (dn_u64)blockIdx.x * DN_BLOCK + threadIdx.x;
   if (row >= n) return;
@@ -90,10 +84,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_panel_f64(double* A, dn_
 
 // A22 -= L21 L21^T below and right of a full diagonal block, the lower triangle only.  Workgroup
 // b of the 1-D grid takes tile (ty, tx) of the tiles with ty >= tx, rows first: b = ty (ty + 1) / 2
-// + tx.  As in dense_update_f64, 4 waves hold a 32 x 32 quarter each as 2 x 2 accumulators of
-// v_mfma_f64_16x16x4_f64 seeded with A22, 8 k-steps; here both operands are rows of L21, so both
-// LDS images are [row][k] with the stride DN_LS: -L21's rows of the tile's rows (A[row = lane & 15]
-// [k = lane >> 4]) and L21's rows of the tile's columns (B[k = lane >> 4][col = lane & 15]).
+// + tx.  Each wave holds a 32 x 32 quarter seeded with A22; both operands are rows of L21, so both
+// LDS images are [row][k]: -L21's rows of the tile's rows and L21's rows of the tile's columns.
 // Rows past n: zeros in LDS, never stored.  Only entries with row >= column are seeded from and
 // stored to A; a quarter wholly above the diagonal (wave 1 of a diagonal tile) does nothing.
 __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_update_f64(double* A, dn_u64 n, dn_u64 lda, dn_u64 j) {
@@ -108,53 +100,29 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_update_f64(double* A, dn
   const unsigned tx = b - (unsigned)((dn_u64)ty * (ty + 1) / 2);
   const dn_u64 r0 = j + DN_NB + (dn_u64)ty * DN_TM;
   const dn_u64 c0 = j + DN_NB + (dn_u64)tx * DN_TN;
-  for (int e = t; e < DN_TM * DN_NB; e += DN_BLOCK) {
+  for (int e = t; e < DN_TM * DN_NB; e += DN_BLOCK) {  // (one loop for both images: their loads are in flight together)
     const int r = e / DN_NB, k = e % DN_NB;
     sA[r][k] = r0 + (dn_u64)r < n ? -A[(r0 + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
     sB[r][k] = c0 + (dn_u64)r < n ? A[(c0 + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0;
   }
   __syncthreads();
-  const int lane = t & 63, w = t >> 6;
-  const int wm = (w >> 1) * 32, wn = (w & 1) * 32;
-  if (ty == tx && wn > wm) return;  // (after the last barrier)
-  const int l15 = lane & 15, l4 = lane >> 4;
+  const TileLane ln = quarter_lane(t);
+  if (ty == tx && ln.wn > ln.wm) return;  // (after the last barrier)
   dn_f64x4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        acc[mi][ni][q] = (r < n && c <= r) ? A[r * lda + c] : 0.0;
-      }
-#pragma unroll
-  for (int ks = 0; ks < DN_NB / 4; ++ks) {
-    double a[2], bv[2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) a[mi] = sA[wm + mi * 16 + l15][ks * 4 + l4];
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) bv[ni] = sB[wn + ni * 16 + l15][ks * 4 + l4];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[mi], bv[ni], acc[mi][ni], 0, 0, 0);
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 r = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    acc[mi][ni][q] = (r < n && c <= r) ? A[r * lda + c] : 0.0;
   }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const dn_u64 r = r0 + (dn_u64)(wm + mi * 16 + l4 + 4 * q), c = c0 + (dn_u64)(wn + ni * 16 + l15);
-        if (r < n && c <= r) A[r * lda + c] = acc[mi][ni][q];
-      }
+  tile_step(acc, ln, sA, [&](int k, int c) { return sB[c][k]; });
+  DN_EACH_ACC(2, 2) {
+    const dn_u64 r = r0 + (dn_u64)ln.row(mi, q), c = c0 + (dn_u64)ln.col(ni);
+    if (r < n && c <= r) A[r * lda + c] = acc[mi][ni][q];
+  }
 }
 
 int launch_potrf(double* A, dn_u64 n, dn_u64 lda, int32_t* info, hipStream_t st) {
   for (dn_u64 j = 0; j < n; j += DN_NB) {
-    const int nb = (int)(n - j < DN_NB ? n - j : DN_NB);
+    const int nb = panel_width(n, j);
     dense_potrf_diag_f64<<<1, DN_BLOCK, 0, st>>>(A, lda, j, nb, info);
     if (j + nb < n) {  // rows below the block: the block is a full one
       const dn_u64 rest = n - j - DN_NB;
