@@ -21,6 +21,10 @@
  *     on the lower triangle (Higham thm 10.3: any summation order, with or without FMA; fp64
  *     sqrt and division are correctly rounded), so a run that ends with *d_info == 0 proves A + E
  *     positive definite for an E within that bound (tests/test_dense_potrf_gpu.py);
+ *   - the solution of fedagg_dense_potrs_f64 from that computed L satisfies the componentwise bound
+ *     |b - A x| <= gamma_{3n+1} |L| |L^T| |x| (Higham thm 10.4: any summation order, with or without
+ *     FMA), and on the positive definite families of tests/test_dense_posv_gpu.py the normwise
+ *     backward error above is at most n u;
  *   - the Householder LQ of fedagg_dense_gelqf_f64 / fedagg_dense_orglq_f64 (A = L Q, n <= m; LAPACK's
  *     dgelqf + dorglq arithmetic with dlarfg's sign, beta = -sign(alpha) ||(alpha, x)||, so Q is
  *     np.linalg.qr(A.T)[0].T with no sign fix-up): the relative residual ||A - L Q||_F / ||A||_2 and
@@ -130,6 +134,25 @@ int fedagg_dense_gelqf_f64(double* d_A, uint64_t n, uint64_t m, uint64_t lda, do
  * rebuilt from d_A and d_tau alone.  d_ws need not be the one gelqf used. */
 int fedagg_dense_orglq_f64(const double* d_A, uint64_t n, uint64_t m, uint64_t lda, const double* d_tau, double* d_Q,
                            uint64_t ldq, void* d_ws, void* stream);
+
+/* ---- The solve from a Cholesky factor and the symmetry test ahead of it (added within ABI version 1) ----
+ * For a Newton system that is symmetric positive definite: symcopy (is it symmetric? and a copy of its
+ * lower triangle, A itself stays intact), fedagg_dense_potrf_f64 on the copy, potrs.  Square matrices
+ * under the conventions above; the leading dimension of a factor is ldl >= n. */
+
+/* *d_flag = 0 if a_ij == a_ji by value for every i >= j, the diagonal included -- np.array_equal(A, A.T):
+ * a NaN anywhere is "not symmetric", -0.0 equals 0.0 -- else 1.  If d_L is not NULL, the lower triangle
+ * of A (row >= column) is copied into it bit for bit, whatever the flag; the strict upper triangle of
+ * d_L and elements [n, ldl) of its rows are never written.  d_A is only read.  d_L = NULL tests only
+ * (ldl is then ignored).  A d_L whose n rows overlap those of d_A is refused. */
+int fedagg_dense_symcopy_f64(const double* d_A, uint64_t n, uint64_t lda, double* d_L, uint64_t ldl, int32_t* d_flag,
+                             void* stream);
+
+/* Solve L L^T x = b from the factor of fedagg_dense_potrf_f64, one right-hand side, in place in d_b:
+ * blocked forward (L) and back (L^T) substitution, with divisions by l_kk (no inverted block).  Only
+ * elements of d_L with row >= column are read.  After a potrf whose *d_info != 0 the factor is
+ * unspecified and so is x. */
+int fedagg_dense_potrs_f64(const double* d_L, uint64_t n, uint64_t ldl, double* d_b, void* stream);
 
 #ifdef __cplusplus
 }

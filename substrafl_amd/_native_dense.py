@@ -1,5 +1,6 @@
 """ctypes binding of ``libfedagg_dense.so`` (the C ABI declared in ``include/fedagg_dense.h``):
-the opt-in dense fp64 LU solve of NewtonRaphson's Newton system on the GPU.
+the opt-in dense fp64 solves of NewtonRaphson's Newton system on the GPU (LU, and Cholesky with its
+symmetry test), the Cholesky of its clients' Hessian check and FedPCA's Householder LQ.
 
 Loaded lazily, by the first call that asks for the device solve: importing ``substrafl_amd`` and
 every default path never touch it.  As with ``libfedagg.so`` there is no fallback: a missing
@@ -37,6 +38,8 @@ SIGNATURES = {
     "fedagg_dense_lq_ws_bytes": (c_u64, [c_u64, c_u64]),
     "fedagg_dense_gelqf_f64": (c_int, [c_void, c_u64, c_u64, c_u64, c_void, c_void, c_void]),
     "fedagg_dense_orglq_f64": (c_int, [c_void, c_u64, c_u64, c_u64, c_void, c_void, c_u64, c_void, c_void]),
+    "fedagg_dense_symcopy_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_u64, c_void, c_void]),
+    "fedagg_dense_potrs_f64": (c_int, [c_void, c_u64, c_u64, c_void, c_void]),
 }
 
 ABI_VERSION = 1

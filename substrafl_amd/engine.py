@@ -1124,12 +1124,15 @@ class AggregationEngine:
         tm["mixed_dtypes"] = not uniform
         return d_out, layout
 
-    # session events of newton_raphson_solve: start, sums done, factorisation done, substitution done
+    # session events of newton_raphson_solve: start, sums done, factorisation done, substitution done;
+    # with method="cholesky" also symcopy done, Cholesky factorisation done, Cholesky substitution done and,
+    # on a fallback, the LU's start
     _EV_NR = (0, 1, 2, 3)
+    _EV_NR_CHOL = (4, 5, 6, 7)
 
     @serialized
     def newton_raphson_solve(self, hessians: List[List[np.ndarray]], gradients: List[List[np.ndarray]],
-                             n_samples: Sequence[int]):
+                             n_samples: Sequence[int], method: str = "lu"):
         """NewtonRaphson's Newton system solved on the device (opt-in; newton_raphson.py:195-213):
         the Hessian and gradient sums exactly as :meth:`sequential_sum` makes them, left in two
         session buffers, then ``fedagg_dense_solve_f64`` (include/fedagg_dense.h: blocked LU with
@@ -1141,9 +1144,24 @@ class AggregationEngine:
         first exactly-zero pivot, or ``(None, 0, reason)`` when the sums are not a float64 Hessian
         with a float32 / float64 gradient -- NumPy solves those in another precision or refuses
         them, so the caller takes the host solve (nothing has run then).  An fp32 gradient sum is
-        widened to fp64 by ``fedagg_cast``, exactly, as NumPy promotes ``solve(f64, f32)``."""
+        widened to fp64 by ``fedagg_cast``, exactly, as NumPy promotes ``solve(f64, f32)``.
+
+        ``method="cholesky"``: the sum of Hessians the clients certified positive definite is
+        symmetric positive definite in the normal case, and pivoting buys nothing.  After the same
+        sums, ``fedagg_dense_symcopy_f64`` (is the sum its own transpose, by value? and a copy of its
+        lower triangle into a second session buffer, with a copy of ``b`` behind it),
+        ``fedagg_dense_potrf_f64`` on the copy and ``fedagg_dense_potrs_f64`` on the copy of ``b``,
+        all enqueued unconditionally; one sync, then the flag, ``info`` and ``x`` come home.  Flag and
+        ``info`` both 0: ``(x, 0, "device: cholesky")``.  Otherwise the Cholesky answer is dropped --
+        no shift, no tolerance -- and the LU above runs on the sums, still intact in HBM: ``x`` and
+        ``info`` are then the bits of ``method="lu"``, and ``reason`` says why (``"device: lu, the
+        Hessian sum does not equal its transpose"`` or ``"device: lu after cholesky info=<j>"``).
+        ``last_timing`` then has ``symcopy_ms``, the Cholesky's ``factor_ms`` and ``substitute_ms``
+        and, after a fallback, the LU's as ``lu_factor_ms`` and ``lu_substitute_ms``."""
         from . import _native_dense
 
+        if method not in ("lu", "cholesky"):
+            raise ValueError(f"method must be 'lu' or 'cholesky', not {method!r}")
         hessians, gradients = native_byte_order(hessians), native_byte_order(gradients)
         h0, g0 = np.asarray(hessians[0][0]), np.asarray(gradients[0][0])
         ht, gt = np.result_type(h0.dtype, 1.0), np.result_type(g0.dtype, 1.0)
@@ -1172,11 +1190,47 @@ class AggregationEngine:
             d_b = d_g
         s.event_record(ev[1])
         ws_bytes = int(lib.fedagg_dense_ws_bytes(P))
-        d_int = s.buffer(self._B_CNT, (P + 1) * 4)  # ipiv, then info
+        d_int = s.buffer(self._B_CNT, (P + 3) * 4)  # ipiv, the LU's info; the Cholesky's flag and info
+        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
+        timing = {"solve": "device", "P": P, "stage_s": tm_h.get("stage_s", 0.0) + tm_g.get("stage_s", 0.0),
+                  "mixed_dtypes": bool(tm_h.get("mixed_dtypes") or tm_g.get("mixed_dtypes"))}
+        x = np.empty(P, np.float64)
+        lu_start, lu_keys = ev[1], ("factor_ms", "substitute_ms")
+        if method == "cholesky":
+            assert ws_bytes == 0  # the LU works in place, so the workspace slot is free for the copy: L, then b
+            evc = self._EV_NR_CHOL
+            d_l = s.buffer(self._B_WS, P * P * 8 + P * 8)
+            d_bc, d_flag, d_cinfo = d_l + P * P * 8, d_int + 4 * (P + 1), d_int + 4 * (P + 2)
+            s._bump(d_l)
+            s._bump(d_int)
+            _native_dense.check(lib.fedagg_dense_symcopy_f64(vp(d_h), P, P, vp(d_l), P, vp(d_flag), st),
+                                "dense_symcopy_f64")
+            s.copy_d2d(d_bc, d_b, P * 8)
+            s.event_record(evc[0])
+            _native_dense.check(lib.fedagg_dense_potrf_f64(vp(d_l), P, P, vp(d_cinfo), st), "dense_potrf_f64")
+            s.event_record(evc[1])
+            _native_dense.check(lib.fedagg_dense_potrs_f64(vp(d_l), P, P, vp(d_bc), st), "dense_potrs_f64")
+            s.event_record(evc[2])
+            s.sync()
+            t1 = time.perf_counter()
+            verdict = np.empty(2, np.int32)  # the flag, the Cholesky's info
+            s.fetch(d_flag, verdict)
+            timing.update(symcopy_ms=s.event_elapsed_ms(ev[1], evc[0]), factor_ms=s.event_elapsed_ms(evc[0], evc[1]),
+                          substitute_ms=s.event_elapsed_ms(evc[1], evc[2]))
+            if verdict[0] == 0 and verdict[1] == 0:
+                s.fetch(d_bc, x)
+                t2 = time.perf_counter()
+                timing.update(solve="device: cholesky", sums_ms=s.event_elapsed_ms(ev[0], ev[1]), fetch_s=t2 - t1,
+                              total_s=t2 - t0)
+                self.last_timing = timing
+                return x, 0, "device: cholesky"
+            timing["solve"] = ("device: lu, the Hessian sum does not equal its transpose" if verdict[0] != 0
+                               else f"device: lu after cholesky info={int(verdict[1])}")
+            lu_start, lu_keys = evc[3], ("lu_factor_ms", "lu_substitute_ms")
+            s.event_record(lu_start)
         d_ws = s.buffer(self._B_WS, ws_bytes) if ws_bytes else 0
         s._bump(d_h)
         s._bump(d_b)
-        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
         _native_dense.check(lib.fedagg_dense_getrf_f64(vp(d_h), P, P, vp(d_int), vp(d_int + 4 * P), vp(d_ws), st),
                             "dense_getrf_f64")
         s.event_record(ev[2])
@@ -1184,17 +1238,14 @@ class AggregationEngine:
         s.event_record(ev[3])
         s.sync()  # so that fetch_s below is the fetch alone, not the wait for the kernels
         t1 = time.perf_counter()
-        x = np.empty(P, np.float64)
         s.fetch(d_b, x)
         info = np.empty(1, np.int32)
         s.fetch(d_int + 4 * P, info)
         t2 = time.perf_counter()
-        self.last_timing = {
-            "solve": "device", "P": P, "stage_s": tm_h.get("stage_s", 0.0) + tm_g.get("stage_s", 0.0),
-            "mixed_dtypes": bool(tm_h.get("mixed_dtypes") or tm_g.get("mixed_dtypes")),
-            "sums_ms": s.event_elapsed_ms(ev[0], ev[1]), "factor_ms": s.event_elapsed_ms(ev[1], ev[2]),
-            "substitute_ms": s.event_elapsed_ms(ev[2], ev[3]), "fetch_s": t2 - t1, "total_s": t2 - t0}
-        return x, int(info[0]), "device"
+        timing.update({"sums_ms": s.event_elapsed_ms(ev[0], ev[1]), lu_keys[0]: s.event_elapsed_ms(lu_start, ev[2]),
+                       lu_keys[1]: s.event_elapsed_ms(ev[2], ev[3]), "fetch_s": t2 - t1, "total_s": t2 - t0})
+        self.last_timing = timing
+        return x, int(info[0]), timing["solve"]
 
     @serialized
     def hessian_cholesky_check(self, H):

@@ -20,7 +20,8 @@ everything of it -- constructor, ``name``, graph building (``build_compute_plan`
   reference's own ``np.linalg.solve`` and unflatten on the host.  Opt-in, ``accelerate(NewtonRaphson,
   solve="device")`` or ``FEDAGG_NR_SOLVE=device``: the dense solve on the GPU too (fp64 LU with
   partial pivoting, ``libfedagg_dense.so``), held to backward-error bounds instead of LAPACK's bits
-  (include/fedagg_dense.h); the default is unchanged.
+  (include/fedagg_dense.h); ``solve="cholesky"``: a Cholesky solve there for a Hessian sum
+  that is symmetric positive definite, that LU for any other; the default is unchanged.
 
 The client half of NewtonRaphson ends every round with an eigenvalue check of its Hessian
 (torch_newton_raphson_algo.py:346-352); :func:`newton_raphson_hessian_check` restates it with an
@@ -69,11 +70,15 @@ def _reference_modules(strategy_cls):
 
 
 def _solve_mode(solve: str) -> str:
-    """``solve`` (``"host"`` or ``"device"``) under the environment override ``FEDAGG_NR_SOLVE``."""
-    mode = os.environ.get("FEDAGG_NR_SOLVE") or solve
-    if mode not in ("host", "device"):
-        raise ValueError(f"solve must be 'host' or 'device', not {mode!r}")
-    return mode
+    """``solve`` (``"host"``, ``"device"`` or ``"cholesky"``) under the environment override
+    ``FEDAGG_NR_SOLVE``."""
+    return _check_solve(os.environ.get("FEDAGG_NR_SOLVE") or solve)
+
+
+def _check_solve(solve: str) -> str:
+    if solve not in ("host", "device", "cholesky"):
+        raise ValueError(f"solve must be 'host', 'device' or 'cholesky', not {solve!r}")
+    return solve
 
 
 def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host"):
@@ -82,13 +87,13 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
     engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
     "all").  ``solve`` matters for NewtonRaphson only: ``"host"`` (the default) keeps the
     reference's ``np.linalg.solve``, bit for bit; ``"device"`` solves the Newton system on the GPU
-    as well (:func:`newton_raphson_update`).  ``FEDAGG_NR_SOLVE=device|host`` overrides it, read
-    when the aggregation runs.  ``qr`` matters for FedPCA only: ``"host"`` (the default) keeps the
-    reference's ``np.linalg.qr`` of each averaged matrix, bit for bit; ``"device"`` orthonormalises
-    each one on the GPU (:func:`strategies.fed_pca.orthonormal_layers`).  ``FEDAGG_PCA_QR=device|host``
+    as well, by LU with partial pivoting; ``"cholesky"`` tries a Cholesky factorisation there first
+    and keeps the LU for a sum that is not symmetric positive definite (:func:`newton_raphson_update`).
+    ``FEDAGG_NR_SOLVE=cholesky|device|host`` overrides it, read when the aggregation runs.  ``qr``
+    matters for FedPCA only: ``"host"`` (the default) keeps the reference's ``np.linalg.qr`` of each
+    averaged matrix, bit for bit; ``"device"`` orthonormalises each one on the GPU (:func:`strategies.fed_pca.orthonormal_layers`).  ``FEDAGG_PCA_QR=device|host``
     overrides it, read when the aggregation runs."""
-    if solve not in ("host", "device"):
-        raise ValueError(f"solve must be 'host' or 'device', not {solve!r}")
+    _check_solve(solve)
     if qr not in ("host", "device"):
         raise ValueError(f"qr must be 'host' or 'device', not {qr!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
@@ -153,7 +158,8 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
         def compute_averaged_states(self, shared_states):
             """newton_raphson.py:151-216: the reference's checks, the two weighted sums on the
             engine, then the reference's own dense solve on the host (``solve="host"``) or the
-            fp64 LU on the device (``solve="device"``), and the reference's unflatten."""
+            fp64 LU on the device (``solve="device"``; ``solve="cholesky"``: a Cholesky ahead of it),
+            and the reference's unflatten."""
             self._check_shared_states(shared_states)
             update = newton_raphson_update(shared_states, self._damping_factor, self._fedagg_device,
                                            solve=self._fedagg_solve)
@@ -197,14 +203,25 @@ def newton_raphson_update(shared_states, damping_factor, device: Optional[Device
     Hessian, which NumPy solves in single precision; fp16, which it refuses) takes the host solve
     and says why in ``last_timing["solve"]``.  An exactly-zero pivot raises NumPy's
     ``LinAlgError("Singular matrix")``.  NaN or Inf in the inputs raise nothing, as with NumPy;
-    what they give is unspecified.  ``FEDAGG_NR_SOLVE`` overrides ``solve``."""
+    what they give is unspecified.  ``FEDAGG_NR_SOLVE`` overrides ``solve``.
+
+    ``solve="cholesky"``: the device route with ``method="cholesky"``.  A Hessian sum that equals its
+    transpose by value and whose Cholesky factorisation runs to completion (``fedagg_dense_potrf_f64``,
+    ``info == 0``) is solved from that factor (``fedagg_dense_potrs_f64``): ``x`` then satisfies
+    ``|b - A x| <= gamma_{3n+1} |L| |L^T| |x|`` (include/fedagg_dense.h), and ``last_timing["solve"]``
+    is ``"device: cholesky"``.  Any other sum gets the LU of ``solve="device"``, bit for bit, after the
+    failed attempt, and ``last_timing["solve"]`` says which of the two it was.  No shift and no
+    tolerance: the Cholesky answer is only ever taken from a factorisation that ran to completion."""
     mode = _solve_mode(solve)
     hessians, gradients, n_samples = _newton_raphson_rows(shared_states)
     eng = engine_for(device)
     eng = eng._single() if hasattr(eng, "_single") else eng  # several GPUs: the first one, as for the sums
     reason = "host"
-    if mode == "device":
-        x, info, reason = eng.newton_raphson_solve(hessians, gradients, n_samples)
+    if mode != "host":
+        if mode == "device":  # (without the keyword: an engine stand-in of before it still fits)
+            x, info, reason = eng.newton_raphson_solve(hessians, gradients, n_samples)
+        else:
+            x, info, reason = eng.newton_raphson_solve(hessians, gradients, n_samples, method="cholesky")
         if x is not None:
             if info != 0:
                 raise np.linalg.LinAlgError("Singular matrix")
