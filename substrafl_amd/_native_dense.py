@@ -82,6 +82,12 @@ def check(rc: int, what: str) -> None:
         raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
 
 
+def call(name: str, *args) -> None:
+    """``fedagg_dense_<name>(*args)``, checked.  Device addresses and the stream go in as plain
+    ``int``: the ``c_void_p`` argtypes of :data:`SIGNATURES` convert them, ``0`` to NULL."""
+    check(getattr(load(), "fedagg_dense_" + name)(*args), "dense_" + name)
+
+
 def blocking() -> tuple:
     """``(panel, tile_m, tile_n)`` of the kernels (``fedagg_dense_blocking``)."""
     a, b, c = c_int(), c_int(), c_int()

@@ -6,8 +6,9 @@
 //   dense_laswp_f64    the panel's row interchanges on the columns left and right of it,
 //   dense_trsm_f64     U12 = L11^-1 A12 (one thread per column, L11 from LDS),
 //   dense_update_f64   A22 -= L21 U12, DN_TM x DN_TN tiles (the tile step of dense_internal.h),
-// then dense_perm_f64 / dense_fwd_f64 / dense_bwd_f64 for the right-hand side.  The stream orders
-// the kernels; no kernel waits on another workgroup, and no sum uses an atomic.
+// then dense_perm_f64 and, per block of DN_NB rows, dense_fwd_f64 / dense_bwd_f64 (the substitution
+// step of dense_internal.h) for the right-hand side.  The stream orders the kernels; no kernel waits
+// on another workgroup, and no sum uses an atomic.
 #include "dense_internal.h"
 
 // The panel kernel's blocking.  DN_NB is dense_internal.h's: the strides below are multiples of it, and the suite
@@ -232,76 +233,13 @@ __global__ void dense_perm_f64(const int32_t* ipiv, dn_u64 n, double* b) {
   }
 }
 
-// Forward substitution, the step of block jb (rows [jb, jb + bs)): every row i >= jb takes off the
-// previous block's finished x (L[i][jb-32 .. jb) . x, k ascending); rows past this block are
-// written back, this block's rows stay in wave 0 of workgroup 0, which solves the unit lower
-// triangle L11 from LDS and writes x in place.  The previous block is only read, this block is
-// read and written by workgroup 0 alone.
+// The substitution steps of dense_internal.h for L U x = P b: L has ones on its diagonal, U is read along rows.
 __global__ __launch_bounds__(DN_BLOCK) void dense_fwd_f64(const double* LU, dn_u64 n, dn_u64 lda, double* b, dn_u64 jb) {
-  __shared__ double sx[DN_NB];
-  __shared__ double sT[DN_NB][DN_NB + 1];
-  const int t = threadIdx.x;
-  const int bs = panel_width(n, jb);
-  const bool has_prev = jb > 0;
-  const dn_u64 prev = jb - DN_NB;
-  if (has_prev && t < DN_NB) sx[t] = b[prev + (dn_u64)t];
-  if (blockIdx.x == 0) load_diag_block(sT, LU, lda, jb, t, [bs](int r, int k) { return k < r && r < bs; });
-  __syncthreads();
-  const dn_u64 i = jb + (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
-  double ri = 0.0;
-  if (i < n) {
-    ri = b[i];
-    if (has_prev) {
-      const double* row = LU + i * lda + prev;
-#pragma unroll
-      for (int k = 0; k < DN_NB; ++k) ri = fma(-row[k], sx[k], ri);
-      if (i >= jb + DN_NB) b[i] = ri;
-    }
-  }
-  if (blockIdx.x == 0 && t < 64) {
-    for (int k = 0; k < bs; ++k) {
-      const double xk = __shfl(ri, k);
-      if (t > k && t < bs) ri = fma(-sT[t][k], xk, ri);
-    }
-    if (t < bs) b[jb + (dn_u64)t] = ri;
-  }
+  subst_fwd_step<true>(LU, n, lda, b, jb);
 }
 
-// Back substitution, the step of block jb, the mirror image: thread q of the grid takes row
-// jb + bs - 1 - q, takes off the block below-right's finished x, and wave 0 of workgroup 0 solves
-// the upper triangle U11 (with its diagonal) for this block's rows.
 __global__ __launch_bounds__(DN_BLOCK) void dense_bwd_f64(const double* LU, dn_u64 n, dn_u64 lda, double* b, dn_u64 jb) {
-  __shared__ double sx[DN_NB];
-  __shared__ double sT[DN_NB][DN_NB + 1];
-  const int t = threadIdx.x;
-  const int bs = panel_width(n, jb);
-  const dn_u64 prev = jb + DN_NB;
-  const bool has_prev = prev < n;
-  const int pbs = has_prev ? panel_width(n, prev) : 0;
-  if (t < DN_NB) sx[t] = t < pbs ? b[prev + (dn_u64)t] : 0.0;
-  if (blockIdx.x == 0) load_diag_block(sT, LU, lda, jb, t, [bs](int r, int k) { return k >= r && k < bs; });
-  __syncthreads();
-  const dn_u64 top = jb + (dn_u64)bs - 1;
-  const dn_u64 q = (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
-  double ri = 0.0;
-  if (q <= top) {
-    const dn_u64 i = top - q;
-    ri = b[i];
-    if (has_prev) {
-      const double* row = LU + i * lda + prev;
-      for (int k = 0; k < pbs; ++k) ri = fma(-row[k], sx[k], ri);
-      if (i < jb) b[i] = ri;
-    }
-  }
-  if (blockIdx.x == 0 && t < 64) {
-    const int r = bs - 1 - t;  // this lane's row of the block (negative: none)
-    for (int kk = bs - 1; kk >= 0; --kk) {
-      if (r == kk) ri = ri / sT[kk][kk];
-      const double xk = __shfl(ri, bs - 1 - kk);
-      if (r >= 0 && r < kk) ri = fma(-sT[r][kk], xk, ri);
-    }
-    if (r >= 0) b[jb + (dn_u64)r] = ri;
-  }
+  subst_bwd_step<false>(LU, n, lda, b, jb);
 }
 
 int launch_getrf(double* A, dn_u64 n, dn_u64 lda, int32_t* ipiv, int32_t* info, hipStream_t st) {
@@ -321,11 +259,7 @@ int launch_getrf(double* A, dn_u64 n, dn_u64 lda, int32_t* ipiv, int32_t* info, 
 
 int launch_getrs(const double* LU, dn_u64 n, dn_u64 lda, const int32_t* ipiv, double* b, hipStream_t st) {
   dense_perm_f64<<<1, 64, 0, st>>>(ipiv, n, b);
-  for (dn_u64 jb = 0; jb < n; jb += DN_NB) dense_fwd_f64<<<blocks_for(n - jb), DN_BLOCK, 0, st>>>(LU, n, lda, b, jb);
-  for (dn_u64 jb = (n - 1) / DN_NB * DN_NB;; jb -= DN_NB) {
-    dense_bwd_f64<<<blocks_for(jb + (dn_u64)panel_width(n, jb)), DN_BLOCK, 0, st>>>(LU, n, lda, b, jb);
-    if (jb == 0) break;
-  }
+  launch_subst(dense_fwd_f64, dense_bwd_f64, LU, n, lda, b, st);
   return check_launch("fedagg_dense_getrs_f64");
 }
 
@@ -355,8 +289,8 @@ int fedagg_dense_getrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipi
   (void)d_ws;
   if (n == 0) return FEDAGG_DENSE_OK;
   if (int rc = check_matrix(d_A, n, lda)) return rc;
-  if (!d_ipiv) return fail(FEDAGG_DENSE_EINVAL, "d_ipiv is NULL");
-  if (!d_info) return fail(FEDAGG_DENSE_EINVAL, "d_info is NULL");
+  if (int rc = check_ptr(d_ipiv, "d_ipiv")) return rc;
+  if (int rc = check_ptr(d_info, "d_info")) return rc;
   return launch_getrf(d_A, n, lda, d_ipiv, d_info, (hipStream_t)stream);
 }
 
@@ -364,8 +298,8 @@ int fedagg_dense_getrs_f64(const double* d_LU, uint64_t n, uint64_t lda, const i
                            void* stream) {
   if (n == 0) return FEDAGG_DENSE_OK;
   if (int rc = check_matrix(d_LU, n, lda)) return rc;
-  if (!d_ipiv) return fail(FEDAGG_DENSE_EINVAL, "d_ipiv is NULL");
-  if (!d_b) return fail(FEDAGG_DENSE_EINVAL, "d_b is NULL");
+  if (int rc = check_ptr(d_ipiv, "d_ipiv")) return rc;
+  if (int rc = check_ptr(d_b, "d_b")) return rc;
   return launch_getrs(d_LU, n, lda, d_ipiv, d_b, (hipStream_t)stream);
 }
 
@@ -374,9 +308,9 @@ int fedagg_dense_solve_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_ipi
   (void)d_ws;
   if (n == 0) return FEDAGG_DENSE_OK;
   if (int rc = check_matrix(d_A, n, lda)) return rc;
-  if (!d_ipiv) return fail(FEDAGG_DENSE_EINVAL, "d_ipiv is NULL");
-  if (!d_info) return fail(FEDAGG_DENSE_EINVAL, "d_info is NULL");
-  if (!d_b) return fail(FEDAGG_DENSE_EINVAL, "d_b is NULL");
+  if (int rc = check_ptr(d_ipiv, "d_ipiv")) return rc;
+  if (int rc = check_ptr(d_info, "d_info")) return rc;
+  if (int rc = check_ptr(d_b, "d_b")) return rc;
   if (int rc = launch_getrf(d_A, n, lda, d_ipiv, d_info, (hipStream_t)stream)) return rc;
   return launch_getrs(d_A, n, lda, d_ipiv, d_b, (hipStream_t)stream);
 }

@@ -1,6 +1,7 @@
 // dense_internal.h -- what the sources of libfedagg_dense.so share: the blocking, the calling
 // thread's error message, the argument checks every entry point makes before its first HIP call,
-// and the device code of the trailing updates: the 32 x 32 block load and the MFMA tile step.
+// and the device code more than one factorisation or solve uses: the 32 x 32 block load, the triangular
+// grid decode, the substitution step of the LU and Cholesky solves, and the MFMA tile step of the updates.
 #ifndef FEDAGG_DENSE_INTERNAL_H
 #define FEDAGG_DENSE_INTERNAL_H
 
@@ -40,7 +41,13 @@ inline int check_launch(const char* what) {
   return FEDAGG_DENSE_EHIP;
 }
 
-// The pieces of the argument checks, before any HIP call: a dimension (named "n" or "m") ...
+// The pieces of the argument checks, before any HIP call: a pointer that must not be NULL, ...
+inline int check_ptr(const void* p, const char* name) {
+  if (!p) return fail(FEDAGG_DENSE_EINVAL, "%s is NULL", name);
+  return FEDAGG_DENSE_OK;
+}
+
+// ... a dimension (named "n" or "m") ...
 inline int check_dim(const char* name, uint64_t v) {
   if (v > FEDAGG_DENSE_MAX_N) return fail(FEDAGG_DENSE_EINVAL, "%s = %lld exceeds FEDAGG_DENSE_MAX_N", name, (long long)v);
   return FEDAGG_DENSE_OK;
@@ -56,7 +63,7 @@ inline int check_ld(const char* name, uint64_t ld, const char* cols_name, uint64
 
 // The argument checks of the square entry points (n >= 1 here).
 inline int check_matrix(const void* d_A, uint64_t n, uint64_t lda) {
-  if (!d_A) return fail(FEDAGG_DENSE_EINVAL, "d_A is NULL");
+  if (int rc = check_ptr(d_A, "d_A")) return rc;
   if (int rc = check_dim("n", n)) return rc;
   return check_ld("lda", lda, "n", n, n);
 }
@@ -79,6 +86,112 @@ template <class P>
 __device__ __forceinline__ void load_diag_block(double (&s)[DN_NB][DN_NB + 1], const double* A, dn_u64 lda, dn_u64 j, int t,
                                                 P keep) {
   each_block_elem(t, [&](int r, int k) { s[r][k] = keep(r, k) ? A[(j + (dn_u64)r) * lda + j + (dn_u64)k] : 0.0; });
+}
+
+// Workgroup b of a 1-D grid over the tiles (ty, tx), ty >= tx, of a lower triangle, rows first:
+// b = ty (ty + 1) / 2 + tx.  The float root is within one of the answer, the two loops settle it.
+__device__ __forceinline__ void lower_tile(unsigned b, unsigned* ty, unsigned* tx) {
+  unsigned y = (unsigned)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
+  while ((dn_u64)y * (y + 1) / 2 > b) --y;
+  while ((dn_u64)(y + 1) * (y + 2) / 2 <= b) ++y;
+  *ty = y;
+  *tx = b - (unsigned)((dn_u64)y * (y + 1) / 2);
+}
+
+// The substitution step: one block of DN_NB rows of a triangular solve with one right-hand side, in place in b.
+// A launch per block, in the order of the sweep; the block finished by the launch before is only read, this block
+// is read and written by workgroup 0 alone.
+//
+// Forward, L x = b with the lower triangle of T, the step of block jb (rows [jb, jb + bs)): every row i >= jb
+// takes off the previous block's finished x (T[i][jb-32 .. jb) . x, k ascending); rows past this block are
+// written back, this block's rows stay in wave 0 of workgroup 0, which solves the triangle L11 from LDS and
+// writes x in place.  UNIT_DIAG: L has ones on its diagonal and T's own is not read (the L of an LU); otherwise
+// a division per row by T's diagonal (a Cholesky factor).
+template <bool UNIT_DIAG>
+__device__ __forceinline__ void subst_fwd_step(const double* T, dn_u64 n, dn_u64 ld, double* b, dn_u64 jb) {
+  __shared__ double sx[DN_NB];
+  __shared__ double sT[DN_NB][DN_NB + 1];
+  const int t = threadIdx.x;
+  const int bs = panel_width(n, jb);
+  const bool has_prev = jb > 0;
+  const dn_u64 prev = jb - DN_NB;
+  if (has_prev && t < DN_NB) sx[t] = b[prev + (dn_u64)t];
+  if (blockIdx.x == 0) load_diag_block(sT, T, ld, jb, t, [bs](int r, int k) { return (UNIT_DIAG ? k < r : k <= r) && r < bs; });
+  __syncthreads();
+  const dn_u64 i = jb + (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
+  double ri = 0.0;
+  if (i < n) {
+    ri = b[i];
+    if (has_prev) {
+      const double* row = T + i * ld + prev;
+#pragma unroll
+      for (int k = 0; k < DN_NB; ++k) ri = fma(-row[k], sx[k], ri);
+      if (i >= jb + DN_NB) b[i] = ri;
+    }
+  }
+  if (blockIdx.x == 0 && t < 64) {
+    for (int k = 0; k < bs; ++k) {
+      if (!UNIT_DIAG && t == k) ri = ri / sT[k][k];
+      const double xk = __shfl(ri, k);
+      if (t > k && t < bs) ri = fma(-sT[t][k], xk, ri);
+    }
+    if (t < bs) b[jb + (dn_u64)t] = ri;
+  }
+}
+
+// Backward, U x = b with a division per row, the step of block jb from the last block up, the mirror image:
+// thread q of the grid takes row i = jb + bs - 1 - q of U, takes off the block below-right's finished x
+// (k ascending), rows above this block are written back, and wave 0 of workgroup 0 solves the triangle U11 for
+// this block's rows.  U is the upper triangle of T, read along T's rows; or, TRANSPOSED, U = L^T for the lower
+// triangle L of T (a Cholesky factor): row i of U is COLUMN i of T, so for one k the threads of a wave read
+// neighbouring elements of T's row prev + k and no thread walks down a column, and element (r, k) of U11 is
+// L11[k][r].
+template <bool TRANSPOSED>
+__device__ __forceinline__ void subst_bwd_step(const double* T, dn_u64 n, dn_u64 ld, double* b, dn_u64 jb) {
+  __shared__ double sx[DN_NB];
+  __shared__ double sT[DN_NB][DN_NB + 1];
+  const int t = threadIdx.x;
+  const int bs = panel_width(n, jb);
+  const dn_u64 prev = jb + DN_NB;
+  const bool has_prev = prev < n;
+  const int pbs = has_prev ? panel_width(n, prev) : 0;
+  if (t < DN_NB) sx[t] = t < pbs ? b[prev + (dn_u64)t] : 0.0;
+  if (blockIdx.x == 0)
+    load_diag_block(sT, T, ld, jb, t, [bs](int r, int k) { return TRANSPOSED ? k <= r && r < bs : k >= r && k < bs; });
+  __syncthreads();
+  const dn_u64 top = jb + (dn_u64)bs - 1;
+  const dn_u64 q = (dn_u64)blockIdx.x * DN_BLOCK + (dn_u64)t;
+  double ri = 0.0;
+  if (q <= top) {
+    const dn_u64 i = top - q;
+    ri = b[i];
+    if (has_prev) {
+      // U[i][prev + k]: TRANSPOSED, rows prev .. prev + pbs of T's column i < prev, below the diagonal
+      const double* u = TRANSPOSED ? T + prev * ld + i : T + i * ld + prev;
+      for (int k = 0; k < pbs; ++k) ri = fma(-u[TRANSPOSED ? (dn_u64)k * ld : (dn_u64)k], sx[k], ri);
+      if (i < jb) b[i] = ri;
+    }
+  }
+  if (blockIdx.x == 0 && t < 64) {
+    const int r = bs - 1 - t;  // this lane's row of the block (negative: none)
+    for (int kk = bs - 1; kk >= 0; --kk) {
+      if (r == kk) ri = ri / sT[kk][kk];
+      const double xk = __shfl(ri, bs - 1 - kk);
+      if (r >= 0 && r < kk) ri = fma(-(TRANSPOSED ? sT[kk][r] : sT[r][kk]), xk, ri);
+    }
+    if (r >= 0) b[jb + (dn_u64)r] = ri;
+  }
+}
+
+// Both sweeps of such a solve on stream st: the forward step for every block from the first down, then the
+// backward step for every block from the last up.  Each grid covers the rows its step still touches.
+typedef void (*subst_kernel)(const double*, dn_u64, dn_u64, double*, dn_u64);
+inline void launch_subst(subst_kernel fwd, subst_kernel bwd, const double* T, dn_u64 n, dn_u64 ld, double* b, hipStream_t st) {
+  for (dn_u64 jb = 0; jb < n; jb += DN_NB) fwd<<<blocks_for(n - jb), DN_BLOCK, 0, st>>>(T, n, ld, b, jb);
+  for (dn_u64 jb = (n - 1) / DN_NB * DN_NB;; jb -= DN_NB) {
+    bwd<<<blocks_for(jb + (dn_u64)panel_width(n, jb)), DN_BLOCK, 0, st>>>(T, n, ld, b, jb);
+    if (jb == 0) break;
+  }
 }
 
 // The tile step: C += A B for a DN_TM x DN_TN (or narrower) tile of C and DN_NB k-values, on

@@ -288,12 +288,12 @@ int launch_orglq(const double* A, dn_u64 n, dn_u64 m, dn_u64 lda, const double* 
 
 // The argument checks of both entry points (n >= 1 here), before any HIP call.
 int check_lq(const void* d_A, dn_u64 n, dn_u64 m, dn_u64 lda, const void* d_tau, const void* d_ws) {
-  if (!d_A) return fail(FEDAGG_DENSE_EINVAL, "d_A is NULL");
+  if (int rc = check_ptr(d_A, "d_A")) return rc;
   if (int rc = check_dim("n", n)) return rc;
   if (int rc = check_dim("m", m)) return rc;
   if (n > m) return fail(FEDAGG_DENSE_EINVAL, "n = %lld is larger than m (the LQ takes n <= m)", (long long)n);
   if (int rc = check_ld("lda", lda, "m", m, n)) return rc;
-  if (!d_tau) return fail(FEDAGG_DENSE_EINVAL, "d_tau is NULL");
+  if (int rc = check_ptr(d_tau, "d_tau")) return rc;
   if (!d_ws) return fail(FEDAGG_DENSE_EINVAL, "d_ws is NULL (fedagg_dense_lq_ws_bytes(n, m) > 0)");
   return FEDAGG_DENSE_OK;
 }
@@ -326,7 +326,7 @@ int fedagg_dense_gelqf_f64(double* d_A, uint64_t n, uint64_t m, uint64_t lda, do
 int fedagg_dense_orglq_f64(const double* d_A, uint64_t n, uint64_t m, uint64_t lda, const double* d_tau, double* d_Q,
                            uint64_t ldq, void* d_ws, void* stream) {
   if (n == 0) return FEDAGG_DENSE_OK;
-  if (!d_Q) return fail(FEDAGG_DENSE_EINVAL, "d_Q is NULL");
+  if (int rc = check_ptr(d_Q, "d_Q")) return rc;
   if (int rc = check_lq(d_A, n, m, lda, d_tau, d_ws)) return rc;
   if (int rc = check_ld("ldq", ldq, "m", m, n)) return rc;
   return launch_orglq(d_A, n, m, lda, d_tau, d_Q, ldq, (double*)d_ws, (hipStream_t)stream);

@@ -83,8 +83,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_panel_f64(double* A, dn_
 }
 
 // A22 -= L21 L21^T below and right of a full diagonal block, the lower triangle only.  Workgroup
-// b of the 1-D grid takes tile (ty, tx) of the tiles with ty >= tx, rows first: b = ty (ty + 1) / 2
-// + tx.  Each wave holds a 32 x 32 quarter seeded with A22; both operands are rows of L21, so both
+// b of the 1-D grid takes tile (ty, tx) of the tiles with ty >= tx, rows first (lower_tile).
+// Each wave holds a 32 x 32 quarter seeded with A22; both operands are rows of L21, so both
 // LDS images are [row][k]: -L21's rows of the tile's rows and L21's rows of the tile's columns.
 // Rows past n: zeros in LDS, never stored.  Only entries with row >= column are seeded from and
 // stored to A; a quarter wholly above the diagonal (wave 1 of a diagonal tile) does nothing.
@@ -92,12 +92,8 @@ __global__ __launch_bounds__(DN_BLOCK) void dense_potrf_update_f64(double* A, dn
   __shared__ double sA[DN_TM][DN_LS];
   __shared__ double sB[DN_TN][DN_LS];
   const int t = threadIdx.x;
-  // (ty, tx) from b: the float root is within one of the answer, the two loops settle it
-  const unsigned b = blockIdx.x;
-  unsigned ty = (unsigned)((sqrt(8.0 * (double)b + 1.0) - 1.0) * 0.5);
-  while ((dn_u64)ty * (ty + 1) / 2 > b) --ty;
-  while ((dn_u64)(ty + 1) * (ty + 2) / 2 <= b) ++ty;
-  const unsigned tx = b - (unsigned)((dn_u64)ty * (ty + 1) / 2);
+  unsigned ty, tx;
+  lower_tile(blockIdx.x, &ty, &tx);
   const dn_u64 r0 = j + DN_NB + (dn_u64)ty * DN_TM;
   const dn_u64 c0 = j + DN_NB + (dn_u64)tx * DN_TN;
   for (int e = t; e < DN_TM * DN_NB; e += DN_BLOCK) {  // (one loop for both images: their loads are in flight together)
@@ -139,6 +135,6 @@ int launch_potrf(double* A, dn_u64 n, dn_u64 lda, int32_t* info, hipStream_t st)
 extern "C" int fedagg_dense_potrf_f64(double* d_A, uint64_t n, uint64_t lda, int32_t* d_info, void* stream) {
   if (n == 0) return FEDAGG_DENSE_OK;
   if (int rc = check_matrix(d_A, n, lda)) return rc;
-  if (!d_info) return fail(FEDAGG_DENSE_EINVAL, "d_info is NULL");
+  if (int rc = check_ptr(d_info, "d_info")) return rc;
   return launch_potrf(d_A, n, lda, d_info, (hipStream_t)stream);
 }

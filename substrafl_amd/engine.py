@@ -1143,19 +1143,15 @@ class AggregationEngine:
         Returns ``(x, info, reason)``: ``x`` float64 of P elements with ``info`` 0 or j + 1 for a
         first exactly-zero pivot, or ``(None, 0, reason)`` when the sums are not a float64 Hessian
         with a float32 / float64 gradient -- NumPy solves those in another precision or refuses
-        them, so the caller takes the host solve (nothing has run then).  An fp32 gradient sum is
-        widened to fp64 by ``fedagg_cast``, exactly, as NumPy promotes ``solve(f64, f32)``.
+        them, so the caller takes the host solve (nothing has run then).
 
         ``method="cholesky"``: the sum of Hessians the clients certified positive definite is
         symmetric positive definite in the normal case, and pivoting buys nothing.  After the same
-        sums, ``fedagg_dense_symcopy_f64`` (is the sum its own transpose, by value? and a copy of its
-        lower triangle into a second session buffer, with a copy of ``b`` behind it),
-        ``fedagg_dense_potrf_f64`` on the copy and ``fedagg_dense_potrs_f64`` on the copy of ``b``,
-        all enqueued unconditionally; one sync, then the flag, ``info`` and ``x`` come home.  Flag and
-        ``info`` both 0: ``(x, 0, "device: cholesky")``.  Otherwise the Cholesky answer is dropped --
-        no shift, no tolerance -- and the LU above runs on the sums, still intact in HBM: ``x`` and
-        ``info`` are then the bits of ``method="lu"``, and ``reason`` says why (``"device: lu, the
-        Hessian sum does not equal its transpose"`` or ``"device: lu after cholesky info=<j>"``).
+        sums, the attempt of :meth:`_nr_cholesky` on a copy of them.  Flag and ``info`` both 0:
+        ``(x, 0, "device: cholesky")``.  Otherwise the Cholesky answer is dropped -- no shift, no
+        tolerance -- and the LU above runs on the sums, still intact in HBM: ``x`` and ``info`` are
+        then the bits of ``method="lu"``, and ``reason`` says why (``"device: lu, the Hessian sum
+        does not equal its transpose"`` or ``"device: lu after cholesky info=<j>"``).
         ``last_timing`` then has ``symcopy_ms``, the Cholesky's ``factor_ms`` and ``substitute_ms``
         and, after a fallback, the LU's as ``lu_factor_ms`` and ``lu_substitute_ms``."""
         from . import _native_dense
@@ -1163,89 +1159,108 @@ class AggregationEngine:
         if method not in ("lu", "cholesky"):
             raise ValueError(f"method must be 'lu' or 'cholesky', not {method!r}")
         hessians, gradients = native_byte_order(hessians), native_byte_order(gradients)
+        P = self._nr_gate(hessians, gradients)
+        if isinstance(P, str):
+            return None, 0, P
+        ws_bytes = int(_native_dense.load().fedagg_dense_ws_bytes(P))
+        s = self.session()
+        t0 = time.perf_counter()
+        d_h, d_b, timing = self._nr_sums(s, hessians, gradients, n_samples, P)
+        d_int = s.buffer(self._B_CNT, (P + 3) * 4)  # ipiv, the LU's info; the Cholesky's flag and info
+        x, info, lu = None, 0, (self._EV_NR[1], "")  # the LU's start event and the prefix of its timing keys
+        if method == "cholesky":
+            assert ws_bytes == 0  # the LU works in place, so the workspace slot is free for the copy: L, then b
+            x, lu = self._nr_cholesky(s, P, d_h, d_b, d_int, timing), (self._EV_NR_CHOL[3], "lu_")
+        if x is None:
+            x, info = self._nr_lu(s, P, d_h, d_b, d_int, ws_bytes, timing, *lu)
+        timing.update(sums_ms=s.event_elapsed_ms(self._EV_NR[0], self._EV_NR[1]), total_s=time.perf_counter() - t0)
+        self.last_timing = timing
+        return x, info, timing["solve"]
+
+    @staticmethod
+    def _nr_gate(hessians, gradients):
+        """The order P of the system the device takes, or the ``"host: ..."`` reason why it does not."""
         h0, g0 = np.asarray(hessians[0][0]), np.asarray(gradients[0][0])
         ht, gt = np.result_type(h0.dtype, 1.0), np.result_type(g0.dtype, 1.0)
         if ht != np.float64:
-            return None, 0, f"host: {np.dtype(ht).name} Hessian sum (NumPy's solve is not a float64 one)"
+            return f"host: {np.dtype(ht).name} Hessian sum (NumPy's solve is not a float64 one)"
         if gt not in (np.float32, np.float64):
-            return None, 0, f"host: {np.dtype(gt).name} gradient sum"
+            return f"host: {np.dtype(gt).name} gradient sum"
         if h0.ndim != 2 or h0.shape[0] != h0.shape[1] or g0.ndim != 1 or g0.shape[0] != h0.shape[0]:
-            return None, 0, f"host: shapes {h0.shape} / {g0.shape} (NumPy's own error applies)"
-        P = int(h0.shape[0])
-        if P == 0:
-            return None, 0, "host: empty system"
-        lib = _native_dense.load()
-        s = self.session()
-        t0 = time.perf_counter()
-        ev = self._EV_NR
-        s.event_record(ev[0])
+            return f"host: shapes {h0.shape} / {g0.shape} (NumPy's own error applies)"
+        if h0.shape[0] == 0:
+            return "host: empty system"
+        return int(h0.shape[0])
+
+    def _nr_sums(self, s, hessians, gradients, n_samples, P: int):
+        """Both sums between events ``_EV_NR[0]`` and ``[1]``, an fp32 gradient sum widened to fp64 by ``fedagg_cast``,
+        exactly, as NumPy promotes ``solve(f64, f32)``.  Returns ``(d_h, d_b, the start of last_timing)``."""
+        s.event_record(self._EV_NR[0])
         d_h, _ = self._sequential_sum_device(hessians, n_samples, self._B_OUT)
         tm_h = self.last_timing
-        d_g, lay_g = self._sequential_sum_device(gradients, n_samples, self._B_COUT)
+        d_b, lay_g = self._sequential_sum_device(gradients, n_samples, self._B_COUT)
         tm_g = self.last_timing
         if lay_g.dtype != np.float64:
-            d_b = s.buffer(self._B_TMP, P * 8)
+            d_g, d_b = d_b, s.buffer(self._B_TMP, P * 8)
             s.cast(d_g, lay_g.dtype, d_b, np.float64, P)
-        else:
-            d_b = d_g
-        s.event_record(ev[1])
-        ws_bytes = int(lib.fedagg_dense_ws_bytes(P))
-        d_int = s.buffer(self._B_CNT, (P + 3) * 4)  # ipiv, the LU's info; the Cholesky's flag and info
-        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
-        timing = {"solve": "device", "P": P, "stage_s": tm_h.get("stage_s", 0.0) + tm_g.get("stage_s", 0.0),
-                  "mixed_dtypes": bool(tm_h.get("mixed_dtypes") or tm_g.get("mixed_dtypes"))}
-        x = np.empty(P, np.float64)
-        lu_start, lu_keys = ev[1], ("factor_ms", "substitute_ms")
-        if method == "cholesky":
-            assert ws_bytes == 0  # the LU works in place, so the workspace slot is free for the copy: L, then b
-            evc = self._EV_NR_CHOL
-            d_l = s.buffer(self._B_WS, P * P * 8 + P * 8)
-            d_bc, d_flag, d_cinfo = d_l + P * P * 8, d_int + 4 * (P + 1), d_int + 4 * (P + 2)
-            s._bump(d_l)
-            s._bump(d_int)
-            _native_dense.check(lib.fedagg_dense_symcopy_f64(vp(d_h), P, P, vp(d_l), P, vp(d_flag), st),
-                                "dense_symcopy_f64")
-            s.copy_d2d(d_bc, d_b, P * 8)
-            s.event_record(evc[0])
-            _native_dense.check(lib.fedagg_dense_potrf_f64(vp(d_l), P, P, vp(d_cinfo), st), "dense_potrf_f64")
-            s.event_record(evc[1])
-            _native_dense.check(lib.fedagg_dense_potrs_f64(vp(d_l), P, P, vp(d_bc), st), "dense_potrs_f64")
-            s.event_record(evc[2])
-            s.sync()
-            t1 = time.perf_counter()
-            verdict = np.empty(2, np.int32)  # the flag, the Cholesky's info
-            s.fetch(d_flag, verdict)
-            timing.update(symcopy_ms=s.event_elapsed_ms(ev[1], evc[0]), factor_ms=s.event_elapsed_ms(evc[0], evc[1]),
-                          substitute_ms=s.event_elapsed_ms(evc[1], evc[2]))
-            if verdict[0] == 0 and verdict[1] == 0:
-                s.fetch(d_bc, x)
-                t2 = time.perf_counter()
-                timing.update(solve="device: cholesky", sums_ms=s.event_elapsed_ms(ev[0], ev[1]), fetch_s=t2 - t1,
-                              total_s=t2 - t0)
-                self.last_timing = timing
-                return x, 0, "device: cholesky"
+        s.event_record(self._EV_NR[1])
+        return d_h, d_b, {"solve": "device", "P": P, "stage_s": tm_h.get("stage_s", 0.0) + tm_g.get("stage_s", 0.0),
+                          "mixed_dtypes": bool(tm_h.get("mixed_dtypes") or tm_g.get("mixed_dtypes"))}
+
+    def _nr_cholesky(self, s, P: int, d_h: int, d_b: int, d_int: int, timing: dict):
+        """The Cholesky attempt, all enqueued unconditionally: ``fedagg_dense_symcopy_f64`` (is the Hessian
+        sum its own transpose, by value? and a copy of its lower triangle into the workspace slot, with a
+        copy of ``b`` behind it), ``fedagg_dense_potrf_f64`` and ``fedagg_dense_potrs_f64`` on the copies;
+        one sync, then the flag, ``info`` and ``x`` come home.  Returns ``x``, or None with the LU's start event
+        recorded; the leg's times and its verdict (``"solve"``) go into ``timing``."""
+        from ._native_dense import call
+        ev1, evc = self._EV_NR[1], self._EV_NR_CHOL
+        x, verdict = np.empty(P, np.float64), np.empty(2, np.int32)  # verdict: the flag, the Cholesky's info
+        d_l = s.buffer(self._B_WS, P * P * 8 + P * 8)
+        d_bc, d_flag, d_cinfo = d_l + P * P * 8, d_int + 4 * (P + 1), d_int + 4 * (P + 2)
+        s._bump(d_l)
+        s._bump(d_int)
+        call("symcopy_f64", d_h, P, P, d_l, P, d_flag, s.stream)
+        s.copy_d2d(d_bc, d_b, P * 8)
+        s.event_record(evc[0])
+        call("potrf_f64", d_l, P, P, d_cinfo, s.stream)
+        s.event_record(evc[1])
+        call("potrs_f64", d_l, P, P, d_bc, s.stream)
+        s.event_record(evc[2])
+        s.sync()
+        t1 = time.perf_counter()
+        s.fetch(d_flag, verdict)
+        timing.update(symcopy_ms=s.event_elapsed_ms(ev1, evc[0]), factor_ms=s.event_elapsed_ms(evc[0], evc[1]),
+                      substitute_ms=s.event_elapsed_ms(evc[1], evc[2]))
+        if verdict[0] != 0 or verdict[1] != 0:
             timing["solve"] = ("device: lu, the Hessian sum does not equal its transpose" if verdict[0] != 0
                                else f"device: lu after cholesky info={int(verdict[1])}")
-            lu_start, lu_keys = evc[3], ("lu_factor_ms", "lu_substitute_ms")
-            s.event_record(lu_start)
+            s.event_record(evc[3])
+            return None
+        s.fetch(d_bc, x)
+        timing.update(solve="device: cholesky", fetch_s=time.perf_counter() - t1)
+        return x
+
+    def _nr_lu(self, s, P: int, d_h: int, d_b: int, d_int: int, ws_bytes: int, timing: dict, start: int, pre: str):
+        """The LU on the sums, in place: ``(x, info)``.  Its two times, the first from event ``start``, go into
+        ``timing`` under the keys ``pre + "factor_ms"`` and ``pre + "substitute_ms"``."""
+        from ._native_dense import call
+        ev = self._EV_NR
         d_ws = s.buffer(self._B_WS, ws_bytes) if ws_bytes else 0
+        x, info = np.empty(P, np.float64), np.empty(1, np.int32)
         s._bump(d_h)
         s._bump(d_b)
-        _native_dense.check(lib.fedagg_dense_getrf_f64(vp(d_h), P, P, vp(d_int), vp(d_int + 4 * P), vp(d_ws), st),
-                            "dense_getrf_f64")
+        call("getrf_f64", d_h, P, P, d_int, d_int + 4 * P, d_ws, s.stream)
         s.event_record(ev[2])
-        _native_dense.check(lib.fedagg_dense_getrs_f64(vp(d_h), P, P, vp(d_int), vp(d_b), st), "dense_getrs_f64")
+        call("getrs_f64", d_h, P, P, d_int, d_b, s.stream)
         s.event_record(ev[3])
         s.sync()  # so that fetch_s below is the fetch alone, not the wait for the kernels
         t1 = time.perf_counter()
         s.fetch(d_b, x)
-        info = np.empty(1, np.int32)
         s.fetch(d_int + 4 * P, info)
-        t2 = time.perf_counter()
-        timing.update({"sums_ms": s.event_elapsed_ms(ev[0], ev[1]), lu_keys[0]: s.event_elapsed_ms(lu_start, ev[2]),
-                       lu_keys[1]: s.event_elapsed_ms(ev[2], ev[3]), "fetch_s": t2 - t1, "total_s": t2 - t0})
-        self.last_timing = timing
-        return x, int(info[0]), timing["solve"]
+        timing.update({"fetch_s": time.perf_counter() - t1, pre + "factor_ms": s.event_elapsed_ms(start, ev[2]),
+                       pre + "substitute_ms": s.event_elapsed_ms(ev[2], ev[3])})
+        return x, int(info[0])
 
     @serialized
     def hessian_cholesky_check(self, H):
@@ -1272,7 +1287,7 @@ class AggregationEngine:
             return None, 0, "host: the Hessian does not equal its transpose"
         from . import _native_dense
 
-        lib = _native_dense.load()
+        _native_dense.load()
         s = self.session()
         t0 = time.perf_counter()
         d_h = s.buffer(self._B_OUT, P * P * 8)
@@ -1282,8 +1297,7 @@ class AggregationEngine:
         ev = self._EV_NR
         s.event_record(ev[0])
         s._bump(d_info)
-        _native_dense.check(lib.fedagg_dense_potrf_f64(ctypes.c_void_p(d_h), P, P, ctypes.c_void_p(d_info),
-                                                       ctypes.c_void_p(s.stream)), "dense_potrf_f64")
+        _native_dense.call("potrf_f64", d_h, P, P, d_info, s.stream)
         s.event_record(ev[1])
         s.sync()  # so that fetch_s below is the fetch alone, not the wait for the kernels
         t2 = time.perf_counter()
@@ -1340,10 +1354,8 @@ class AggregationEngine:
             s.cast(d_narrow, np.float32, d_a, np.float64, n * m)  # exact
         for d in (d_a, d_q, d_tau, d_ws):
             s._bump(d)
-        vp, st = ctypes.c_void_p, ctypes.c_void_p(s.stream)
-        _native_dense.check(lib.fedagg_dense_gelqf_f64(vp(d_a), n, m, m, vp(d_tau), vp(d_ws), st), "dense_gelqf_f64")
-        _native_dense.check(lib.fedagg_dense_orglq_f64(vp(d_a), n, m, m, vp(d_tau), vp(d_q), m, vp(d_ws), st),
-                            "dense_orglq_f64")
+        _native_dense.call("gelqf_f64", d_a, n, m, m, d_tau, d_ws, s.stream)
+        _native_dense.call("orglq_f64", d_a, n, m, m, d_tau, d_q, m, d_ws, s.stream)
         if not wide:
             s.cast(d_q, np.float64, d_narrow, np.float32, n * m)  # NumPy's astype rounding
         s.event_record(ev[1])

@@ -74,6 +74,30 @@ def test_bad_arguments_are_refused_before_any_hip_call():
         _native_dense.check(-1, "x")
 
 
+def test_call_takes_plain_ints_for_pointers_and_keeps_the_error_text():
+    """``_native_dense.call``: the engine passes device addresses and the stream as ``int``."""
+    # what the declared argtypes make of an int, without the library: labs() hands its argument back
+    labs = ctypes.CDLL(None).labs
+    labs.restype, labs.argtypes = ctypes.c_long, [_native_dense.c_void]
+    assert labs(0x7F0012345678) == 0x7F0012345678 and labs(0) == 0
+    with pytest.raises(ctypes.ArgumentError):
+        labs(1.0)
+    for name, (_, args) in _native_dense.SIGNATURES.items():
+        if name.endswith("_f64"):  # every entry point the engine reaches through call()
+            assert set(args) <= {_native_dense.c_void, _native_dense.c_u64}, name
+    # the library's argument checks come before any HIP call: no address below is dereferenced
+    L, B = 0x1000, 0x2000
+    assert _native_dense.call("potrs_f64", 0, 0, 0, 0, 0) is None  # n == 0
+    with pytest.raises(_native.NativeLibraryError, match=r"^dense_potrs_f64 failed \(-1\): d_L is NULL$"):
+        _native_dense.call("potrs_f64", 0, 4, 4, B, 0)
+    with pytest.raises(_native.NativeLibraryError, match=r"^dense_potrs_f64 failed \(-1\): d_b is NULL$"):
+        _native_dense.call("potrs_f64", L, 4, 4, 0, 0)
+    with pytest.raises(_native.NativeLibraryError, match=r"^dense_getrf_f64 failed \(-1\): lda = 3 is smaller than n$"):
+        _native_dense.call("getrf_f64", L, 4, 3, B, B, 0, 0)
+    with pytest.raises(_native.NativeLibraryError, match=r"^dense_symcopy_f64 failed \(-1\): d_flag is NULL$"):
+        _native_dense.call("symcopy_f64", L, 4, 4, 0, 4, 0, 0)
+
+
 def test_missing_dense_library_is_loud_and_names_the_host_solve(monkeypatch, tmp_path):
     monkeypatch.setattr(_native_dense, "_lib", None)
     monkeypatch.setattr(_native_dense, "LIB_PATH", tmp_path / "nope.so")
