@@ -1,5 +1,5 @@
 """Build hook of the installable package (pyproject.toml): ``build_py`` also compiles
-``libfedagg.so``, ``libfedagg_dense.so`` and ``libfedagg_promote.so`` for gfx950 into the build tree with the same compiler, flags and object cache as
+``libfedagg.so``, ``libfedagg_dense.so``, ``libfedagg_promote.so`` and ``libfedagg_mx.so`` for gfx950 into the build tree with the same compiler, flags and object cache as
 ``__graft_entry__.build()``, so the wheel carries the HIP library next to the Python package.
 No hipcc, no wheel: ``compile_library`` raises, and the build fails loudly."""
 
@@ -23,6 +23,7 @@ class BuildPyWithHip(build_py):
         __graft_entry__.compile_library(pkg / "libfedagg.so")
         __graft_entry__.compile_dense_library(pkg / "libfedagg_dense.so")
         __graft_entry__.compile_promote_library(pkg / "libfedagg_promote.so")
+        __graft_entry__.compile_mx_library(pkg / "libfedagg_mx.so")
 
 
 class BinaryDistribution(Distribution):

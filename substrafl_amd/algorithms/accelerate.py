@@ -68,6 +68,8 @@ def _reference_base(algo_cls):
 
 
 def _export(self, tensors, tag="export"):
+    if getattr(self, "_fedagg_mxfp8", False):
+        return wm.export_mxfp8(tensors, tag=tag)
     return wm.export_numpy(tensors, wire=self._fedagg_wire, tag=tag)
 
 
@@ -259,14 +261,23 @@ def _registering_init(base_init):
 def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
     """A subclass of ``algo_cls`` (SubstraFL's ``TorchFedAvgAlgo`` / ``TorchScaffoldAlgo`` /
     ``TorchNewtonRaphsonAlgo`` or a subclass of one) whose ``train`` moves weights with the
-    flat-bucket kernels.  ``wire``: export :class:`..wire.BucketArray` layers instead of plain
-    arrays.  ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
+    flat-bucket kernels.  ``wire``: ``True`` exports :class:`..wire.BucketArray` layers instead of plain
+    arrays; ``"mxfp8"`` (FedAvg only; a ``TypeError`` for the others, any other string a
+    ``ValueError``) quantises the update of an fp32 or bf16 model on the device to OCP MXFP8
+    (:func:`.weight_manager.export_mxfp8`: 1.03 bytes per parameter in one buffer; the aggregator's
+    fp32 average comes back and is applied by the existing paths; no error feedback or residual
+    is carried between rounds).  ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
     default, keeps the reference's eigenvalue check and never loads the dense library;
     ``"device"`` tries a Cholesky certificate on the GPU first
     (:func:`..integration.newton_raphson_hessian_check`; ``FEDAGG_NR_CHECK`` overrides it when
     ``train`` runs)."""
     base = _reference_base(algo_cls)
     kind = _BASES[base.__name__]
+    if isinstance(wire, str) and wire != "mxfp8":
+        raise ValueError(f"wire must be True, False or 'mxfp8', not {wire!r}")
+    mxfp8 = wire == "mxfp8"
+    if mxfp8 and kind != "fedavg":
+        raise TypeError(f"wire='mxfp8' is an option of TorchFedAvgAlgo, not of {base.__name__}")
     if kind != "newton_raphson" and hessian_check is not None:
         raise TypeError(f"hessian_check is an option of TorchNewtonRaphsonAlgo, not of {base.__name__}")
     if kind == "newton_raphson" and hessian_check not in (None, "host", "device"):
@@ -276,6 +287,7 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
     schemas = importlib.import_module(f"{pkg}.strategies.schemas")
     ns = {"__doc__": f"{algo_cls.__name__} with its weight moves on MI355X (substrafl_amd.accelerate_algo).",
           "_fedagg_wire": bool(wire),
+          "_fedagg_mxfp8": mxfp8,
           "__init__": _registering_init(algo_cls.__init__),
           "__module__": __name__}  # type() under ABCMeta would otherwise record "abc"
     if kind == "newton_raphson":

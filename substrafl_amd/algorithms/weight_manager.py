@@ -370,6 +370,39 @@ def _host_array(t: torch.Tensor) -> np.ndarray:
     return t.numpy()
 
 
+def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export") -> List[np.ndarray]:
+    """The MXFP8 form of ``tensors`` (``wire.py``: L ``wire.E4M3`` layers, then one ``wire.E8M0``
+    scale array over the raveled concatenation), quantised on the device by
+    ``fedagg_mx_quantize`` from the flat fp32 or bf16 bucket.  Codes and scales share one device
+    buffer (the scales right behind the codes), so they leave in ONE D2H copy into one host
+    buffer, and the layers returned are :class:`wire.BucketArray` views of it: they pickle as that
+    one buffer.  Anything but fp32 or bf16 tensors on a ROCm device is refused
+    (``NotImplementedError``): there is no host quantiser behind this and the fp32 average could
+    not go back onto an fp16 or fp64 model through the flat kernels."""
+    from .. import _native_mx, runtime
+    from ..wire import E4M3, E8M0, MX_BLOCK
+
+    tensors = list(tensors)
+    kind = _kind(tensors)
+    if kind not in (_native.FEDAGG_F32, _native.FEDAGG_BF16):
+        dts = sorted({str(t.dtype) for t in tensors})
+        raise NotImplementedError(f"wire='mxfp8': the update of an fp32 or bf16 model on a ROCm device is quantised, "
+                                  f"got {dts} on {sorted({str(t.device) for t in tensors})}")
+    flat = flat_bucket(tensors)
+    if flat is None:
+        flat = _gather_flat(tensors)
+    M = flat.numel()
+    n_scales = -(-M // MX_BLOCK)
+    dev = torch.empty(M + n_scales, dtype=torch.uint8, device=flat.device)
+    _native_mx.quantize(flat.data_ptr(), kind, M, dev.data_ptr(), dev.data_ptr() + M, _stream(flat.device))
+    host = runtime.reusable_host_array(M + n_scales, np.dtype(np.uint8), tag)
+    torch.cuda.current_stream(flat.device).synchronize()  # the quantiser ran on torch's stream
+    with runtime.device_lock(flat.device.index):  # the session's ring is shared with the engine
+        runtime.session(flat.device.index).fetch(dev.data_ptr(), host)
+    shapes = [tuple(t.shape) for t in tensors]
+    return bucket_views(host, shapes + [(n_scales,)], [E4M3] * len(shapes) + [E8M0])
+
+
 def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = "export") -> List[np.ndarray]:
     """``[p.cpu().detach().numpy() for p in ...]`` (torch_fed_avg_algo.py:227-230) with ONE D2H copy
     when the tensors are views of one flat bucket.  With ``wire`` the arrays returned are

@@ -38,7 +38,7 @@ import numpy as np
 
 from . import _native, handoff, runtime
 from .layout import BucketLayout
-from .wire import BF16, flat_of
+from .wire import BF16, E4M3, E8M0, MX_BLOCK, flat_of, has_mxfp8, mxfp8_check
 
 KINDS = ("f32", "bf16", "f64", "f16")
 BF16_GROUP = "bf16"  # fedavg()'s dtype-group key of wire.BF16 layers (the others are NumPy dtype strings)
@@ -88,6 +88,17 @@ def reject_bf16(rows, what: str) -> None:
             if getattr(a, "dtype", None) == BF16:
                 raise NotImplementedError(f"{what}: no bf16 path for wire.BF16 layers "
                                           "(FedAvg on one GPU aggregates them)")
+
+
+def reject_mxfp8(rows, what: str) -> None:
+    """MXFP8 updates (``wire.E4M3`` codes, ``wire.E8M0`` scales) hold bit patterns: only FedAvg on
+    the single-GPU in-core route (:meth:`AggregationEngine.fedavg_mxfp8`) decodes them, every
+    other route refuses them by name."""
+    for row in rows:
+        for a in row:
+            if getattr(a, "dtype", None) in (E4M3, E8M0):
+                raise NotImplementedError(f"{what}: no MXFP8 path for wire.E4M3 / wire.E8M0 arrays "
+                                          "(FedAvg on one GPU, in core, aggregates them)")
 
 
 def native_byte_order(rows):
@@ -918,6 +929,8 @@ class AggregationEngine:
         whose buckets exceed the budget are streamed through the GPU in parameter ranges
         (``MultiDeviceEngine.fedavg_routed`` with this one device) where :meth:`fedavg` refuses
         them; that refusal is pinned by tests, so the route is this name."""
+        if parameters_updates and any(has_mxfp8(pu) for pu in parameters_updates):
+            return self.fedavg_mxfp8(parameters_updates, n_samples, wire)  # the MXFP8 wire (DESIGN §2)
         if (parameters_updates and parameters_updates[0]
                 and all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
             out = self._fedavg_bf16_out_of_core(parameters_updates, n_samples, wire)
@@ -935,6 +948,93 @@ class AggregationEngine:
         out = ooc.fedavg_routed(parameters_updates, n_samples, wire)
         self.last_timing = {"out_of_core": ooc.last_timing, "staging": "out-of-core"}
         return out
+
+    # ----------------------------------------------------------------------------------
+    def fedavg_mxfp8(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
+                     wire: bool = False) -> List[np.ndarray]:
+        """FedAvg over MXFP8 updates (``[layer_0 .. layer_{L-1}, scales]``, ``wire.E4M3`` layers and
+        one trailing ``wire.E8M0`` array per client): bit-identical to fed_avg.py:217-222 on the
+        exactly decoded fp32 inputs (``wire.mxfp8_to_float32``).  The K code rows and the K scale
+        rows are staged as two byte buckets, ``fedagg_mx_fedavg_e4m3`` reduces them in one call and
+        the L fp32 layers come home (``wire``: as :class:`wire.BucketArray` layers of one bucket).
+
+        Refused before any device work: clients of which only some are MXFP8
+        (``NotImplementedError``), a scale array that is missing or has the wrong dtype or length,
+        layer shapes that differ between clients (``ValueError``), numel == 1 layers over more
+        clients than the library's pairwise patch serves, the device hand-off and buckets beyond
+        the in-core budget (``NotImplementedError``, each naming its route)."""
+        from . import _native_mx
+
+        K = len(parameters_updates)
+        n_mx = sum(1 for pu in parameters_updates if has_mxfp8(pu))
+        if n_mx != K:
+            raise NotImplementedError(f"FedAvg engine: {n_mx} of {K} clients sent MXFP8 updates; the MXFP8 route "
+                                      "takes MXFP8 from every client or from none")
+        Ms = [mxfp8_check(pu) for pu in parameters_updates]
+        shapes = [tuple(np.shape(a)) for a in parameters_updates[0][:-1]]
+        for pu in parameters_updates[1:]:
+            if [tuple(np.shape(a)) for a in pu[:-1]] != shapes:
+                raise ValueError("FedAvg engine: MXFP8 layer shapes differ between clients")
+        M = Ms[0]
+        layout = BucketLayout(range(len(shapes)), shapes, np.uint8)
+        if layout.pairwise_idx.size and K > _native_mx.MAX_PAIRWISE_K:
+            raise NotImplementedError(f"FedAvg engine: the MXFP8 route serves numel == 1 layers up to "
+                                      f"{_native_mx.MAX_PAIRWISE_K} clients (got {K})")
+        if handoff.enabled():
+            raise NotImplementedError("FedAvg engine: the device hand-off has no MXFP8 route")
+        return self._fedavg_mxfp8(parameters_updates, n_samples, wire, layout, shapes, M)
+
+    @serialized
+    def _fedavg_mxfp8(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, shapes, M: int):
+        from . import _native_mx
+
+        t_start = time.perf_counter()
+        K = len(parameters_updates)
+        n_scales = -(-M // MX_BLOCK)
+        ld_s = -(-n_scales // 256) * 256
+        need = K * (layout.ld + ld_s) + 4 * layout.ld
+        slots = (self._B_BUCKET, self._B_CV, self._B_OUT)
+        if self.max_bucket_bytes is not None:
+            budget = int(self.max_bucket_bytes)
+        else:
+            from .multi_device import HBM_HEADROOM
+
+            budget = int((runtime.device_memory(self._index())[0] + self.session().held_bytes(slots)) * HBM_HEADROOM)
+        if need > budget:
+            raise NotImplementedError(f"FedAvg engine: the out-of-core route has no MXFP8 path ({need} bytes do "
+                                      "not fit the bucket budget)")
+        s = self.session()
+        self.last_timing = tm = {}
+        self._prestaged = {}
+
+        def byte_rows(arrays):
+            f = flat_of(arrays)  # a client that arrived as one bucket: one segment
+            if f is not None:
+                return [f.view(np.uint8)]
+            return [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+
+        t0 = time.perf_counter()
+        d_codes = s.buffer(self._B_BUCKET, K * layout.ld)
+        s.stage(d_codes, layout.ld, [byte_rows(pu[:-1]) for pu in parameters_updates])
+        d_scales = s.buffer(self._B_CV, K * ld_s)
+        s.stage(d_scales, ld_s, [byte_rows(pu[-1:]) for pu in parameters_updates])
+        tm["staging"] = "mxfp8-host-rows"
+        tm["prestaged"] = False
+        tm["layout"] = "rows"
+        tm["stage_s"] = time.perf_counter() - t0
+        d_out = s.buffer(self._B_OUT, layout.ld * 4)
+        t1 = time.perf_counter()
+        _native_mx.fedavg_e4m3([d_codes + k * layout.ld for k in range(K)], [d_scales + k * ld_s for k in range(K)],
+                               fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx, d_out, s.stream)
+        out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp8")
+        s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        results: List[Optional[np.ndarray]] = [None] * len(shapes)
+        for li, arr in BucketLayout(range(len(shapes)), shapes, np.float32).unpack(out, wire):
+            results[li] = arr
+        tm.update({f"native_{k}": v for k, v in s.timing().items()})
+        tm["total_s"] = time.perf_counter() - t_start
+        return results  # type: ignore[return-value]
 
     # ----------------------------------------------------------------------------------
     @serialized
@@ -1408,6 +1508,7 @@ class AggregationEngine:
             return 0, [], []
         lists = (parameters_updates, control_variate_updates, server_control_variates)
         for lst in lists:
+            reject_mxfp8(lst, "Scaffold engine")
             reject_bf16(lst, "Scaffold engine")
             for client in lst:
                 for a in client:

@@ -36,7 +36,7 @@ import numpy as np
 from . import _native, runtime
 from .engine import (KIND_CODES, TILED_KINDS, AggregationEngine, FedAvgPlan, ScaffoldBucketPlan, ScaffoldPlan,
                      TiledFedAvgPlan, bucket_dtype16, direct_rows, equal_count, fedavg_weights, kind_of,
-                     native_byte_order, reject_bf16, scaffold_bucket_dtypes, scaffold_weights, serialized, tiled_elems,
+                     native_byte_order, reject_bf16, reject_mxfp8, scaffold_bucket_dtypes, scaffold_weights, serialized, tiled_elems,
                      tiled_recommended, tiled_tile)
 from .layout import ROW_ALIGN_BYTES, BucketLayout
 from .sharding import SHARD_ALIGN, shard_bounds
@@ -289,6 +289,7 @@ class MultiDeviceEngine:
         L = len(parameters_updates[0])
         if L == 0:
             return []
+        reject_mxfp8(parameters_updates, "MultiDeviceEngine.fedavg (several devices, or out of core)")
         reject_bf16(parameters_updates, "MultiDeviceEngine.fedavg")
         dts = {a.dtype for pu in parameters_updates for a in pu}
         R = np.result_type(next(iter(dts)), 1.0) if len(dts) == 1 else None
@@ -361,6 +362,7 @@ class MultiDeviceEngine:
         ``fedagg_fedavg_bf16`` / ``_tiled_bf16`` launch, ``K * 2 + 4`` bytes of HBM per element), bit-
         identical to :class:`engine.AggregationEngine` on one GPU.  :meth:`fedavg` itself keeps
         refusing ``wire.BF16`` (its refusal is pinned by tests), so the route is this name."""
+        reject_mxfp8(parameters_updates, "MultiDeviceEngine.fedavg_routed (several devices, or out of core)")
         if (not parameters_updates or not parameters_updates[0]
                 or not all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
             return self.fedavg(parameters_updates, n_samples, wire)
@@ -385,6 +387,8 @@ class MultiDeviceEngine:
         if L == 0:
             return 0, [], []
         lists = (parameters_updates, control_variate_updates, server_control_variates)
+        for lst in lists:
+            reject_mxfp8(lst, "MultiDeviceEngine.scaffold")
         dts = {a.dtype for lst in lists for client in lst for a in client}
         shapes = [[a.shape for a in lst[0]] for lst in lists]
         uniform = len(dts) == 1 and next(iter(dts)) in (np.float32, np.float64)

@@ -878,6 +878,9 @@ def _one_dtype(lists, what: str) -> np.dtype:
     """The single float dtype every array of ``lists`` carries (the sharded host entry points
     stage raw bytes; mixed or integer layers go through the single-process engines, which apply
     NumPy's promotion on the device)."""
+    from .engine import reject_mxfp8
+
+    reject_mxfp8(lists, f"client-sharded {what}")
     dts = {a.dtype for row in lists for a in row}
     if len(dts) != 1 or next(iter(dts)) not in (np.float16, np.float32, np.float64):
         raise NotImplementedError(f"sharded {what}: every layer of every client must have one float dtype "

@@ -59,6 +59,146 @@ def float32_to_bf16(a) -> np.ndarray:
     return r.view(BF16)
 
 
+# ------------------------------------------------------------------------------------------
+# OCP MXFP8: 1-byte ``e4m3fn`` elements, one ``e8m0`` power-of-two scale per block of 32.
+#
+# A quantised update is ``[layer_0 .. layer_{L-1}, scales]``: every layer an array of the layer's
+# shape and dtype :data:`E4M3`, then ONE trailing 1-D :data:`E8M0` array of ``ceil(M / 32)`` scale
+# bytes, M the sum of the layers' numels.  Blocks run over the concatenation of the raveled layers
+# in list order with no padding between layers: block b covers flat elements
+# ``[32 b, min(32 b + 32, M))`` and may span layers.
+#
+# Decode.  A code c has sign S, exponent field E (4 bits) and mantissa field m (3 bits):
+# ``v = (-1)^S m 2^-9`` if E == 0, else ``(-1)^S (8 + m) 2^(E - 10)``; 0x7F and 0xFF are NaN and
+# there is no infinity (``e4m3fn``, not ``fnuz``).  With the block's scale byte s the element is
+# ``fl32(v 2^(s - 127))``; s == 255 makes the whole block NaN.  Every finite product is an fp32
+# value (the smallest granule is 2^-136, an fp32 subnormal; nothing is flushed); the one inexact
+# case is overflow to +-inf (448 x 2^127).
+#
+# Encode, per block, amax = max |x_i|: any NaN or Inf: s = 255 and every code 0x00.  amax == 0:
+# s = 127 and the codes carry the zeros' signs.  Else e = floor(log2(amax)) - 8, e += 1 if
+# amax 2^-e > 464 (464 is the tie that still rounds to 448, so nothing saturates), e clamped to
+# [-127, 127], s = e + 127; an element is y = fl32(x 2^-e) rounded to nearest even among the
+# e4m3fn values, |y| >= 448 to +-448, the sign of zero kept.
+#
+# Like BF16 these are structured dtypes NumPy refuses arithmetic on.
+E4M3 = np.dtype([("e4m3fn", "u1")])
+E8M0 = np.dtype([("e8m0", "u1")])
+MX_BLOCK = 32
+
+
+def is_mxfp8(parameters_update) -> bool:
+    """Whether ``parameters_update`` has the MXFP8 form: :data:`E4M3` layers, then one trailing
+    :data:`E8M0` array (its length is checked by :func:`mxfp8_check`)."""
+    pu = list(parameters_update) if isinstance(parameters_update, (list, tuple)) else None
+    return bool(pu) and len(pu) >= 2 and getattr(pu[-1], "dtype", None) == E8M0 and all(
+        getattr(a, "dtype", None) == E4M3 for a in pu[:-1])
+
+
+def has_mxfp8(parameters_update) -> bool:
+    """Whether any array of ``parameters_update`` carries :data:`E4M3` or :data:`E8M0`."""
+    return any(getattr(a, "dtype", None) in (E4M3, E8M0) for a in parameters_update)
+
+
+def mxfp8_check(parameters_update) -> int:
+    """M of an MXFP8 update; ``ValueError`` when the scale array is missing, is not the one
+    trailing 1-D :data:`E8M0` array, or does not hold ``ceil(M / 32)`` bytes."""
+    pu = list(parameters_update)
+    if not pu or getattr(pu[-1], "dtype", None) != E8M0:
+        raise ValueError("MXFP8 update: the trailing wire.E8M0 scale array is missing")
+    layers = pu[:-1]
+    if not layers or any(getattr(a, "dtype", None) != E4M3 for a in layers):
+        raise ValueError("MXFP8 update: every layer before the scale array must have dtype wire.E4M3")
+    M = sum(int(np.asarray(a).size) for a in layers)
+    s = np.asarray(pu[-1])
+    if s.ndim != 1 or s.size != -(-M // MX_BLOCK):
+        raise ValueError(f"MXFP8 update: {M} elements need a 1-D scale array of {-(-M // MX_BLOCK)} bytes, "
+                         f"got shape {s.shape}")
+    return M
+
+
+def _e4m3_round(y: np.ndarray) -> np.ndarray:
+    """fp32 ``y`` (finite) to e4m3fn codes: nearest even, |y| >= 448 to +-448, signed zeros."""
+    u = np.ascontiguousarray(y, np.float32).view(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    # below 2^-6 the e4m3fn values are the multiples of 2^-9: |y| + 2^14 rounds there (fp32 ulp 2^-9)
+    with np.errstate(all="ignore"):
+        sub = (a.view(np.float32) + np.float32(16384.0)).view(np.uint32) - np.uint32(0x46800000)
+    a_n = np.minimum(a, np.uint32(0x43E00000))  # 448: keeps the shifts below in range
+    nrm = (a_n + np.uint32(0x7FFFF) + ((a_n >> np.uint32(20)) & np.uint32(1)) - np.uint32(0x3C000000)) >> np.uint32(20)
+    code = np.where(a < np.uint32(0x3C800000), sub, nrm)
+    code = np.where(a >= np.uint32(0x43E00000), np.uint32(0x7E), code)
+    return (code | ((u >> np.uint32(24)) & np.uint32(0x80))).astype(np.uint8)
+
+
+def _mx_encode_flat(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    M = x.size
+    nb = -(-M // MX_BLOCK)
+    pad = np.zeros(nb * MX_BLOCK, np.float32)
+    pad[:M] = x
+    pad = pad.reshape(nb, MX_BLOCK)
+    a = (pad.view(np.uint32) & np.uint32(0x7FFFFFFF)).max(axis=1) if nb else np.zeros(0, np.uint32)
+    bad = a >= np.uint32(0x7F800000)
+    zero = a == 0
+    amax = a.view(np.float32).astype(np.float64)
+    amax[bad | zero] = 1.0
+    e = np.frexp(amax)[1].astype(np.int64) - 9  # floor(log2(amax)) - 8
+    e += np.ldexp(amax, -e) > 464.0
+    e = np.clip(e, -127, 127)
+    e[bad | zero] = 0
+    s = (e + 127).astype(np.uint8)
+    s[bad] = 255
+    inv = np.ldexp(1.0, -e).astype(np.float32)  # 2^-e, exact (2^-127 is an fp32 subnormal)
+    with np.errstate(all="ignore"):
+        y = pad * inv[:, None]
+    codes = _e4m3_round(y)
+    codes[bad, :] = 0
+    return codes.reshape(-1)[:M].copy(), s
+
+
+def float32_to_mxfp8(x):
+    """``x`` (an array, or a list of layers; cast to fp32) encoded by the rule above:
+    ``(codes, scales)`` with ``codes`` of dtype :data:`E4M3` shaped like ``x`` (a list of such
+    arrays for a list) and ``scales`` the 1-D :data:`E8M0` array over the raveled concatenation."""
+    many = isinstance(x, (list, tuple))
+    arrs = [np.asarray(a, dtype=np.float32) for a in (x if many else [x])]
+    flat = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.float32)
+    codes, s = _mx_encode_flat(flat)
+    out, off = [], 0
+    for a in arrs:
+        out.append(codes[off : off + a.size].reshape(a.shape).view(E4M3))
+        off += a.size
+    return (out if many else out[0]), s.view(E8M0)
+
+
+def mxfp8_to_float32(codes, scales):
+    """The exact fp32 values of MXFP8 ``codes`` (an :data:`E4M3` array, or a list of layers) under
+    the :data:`E8M0` ``scales`` of their raveled concatenation; the shape(s) of ``codes``."""
+    many = isinstance(codes, (list, tuple))
+    arrs = [np.asarray(a) for a in (codes if many else [codes])]
+    scales = np.asarray(scales)
+    if any(a.dtype != E4M3 for a in arrs) or scales.dtype != E8M0:
+        raise TypeError("mxfp8_to_float32: expected wire.E4M3 codes and wire.E8M0 scales")
+    c = np.concatenate([a["e4m3fn"].reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.uint8)
+    s = scales["e8m0"].reshape(-1)
+    M = c.size
+    if s.size != -(-M // MX_BLOCK):
+        raise ValueError(f"mxfp8_to_float32: {M} elements need {-(-M // MX_BLOCK)} scale bytes, got {s.size}")
+    E = ((c >> 3) & 15).astype(np.int64)
+    m = (c & 7).astype(np.float64)
+    mag = np.where(E == 0, m * 2.0 ** -9, np.ldexp(8.0 + m, E - 10))
+    mag[(c & 0x7F) == 0x7F] = np.nan
+    sc = np.ldexp(1.0, s.astype(np.int64) - 127)
+    sc[s == 255] = np.nan
+    with np.errstate(all="ignore"):
+        v = np.copysign(mag * np.repeat(sc, MX_BLOCK)[:M], np.where(c & 0x80, -1.0, 1.0)).astype(np.float32)
+    out, off = [], 0
+    for a in arrs:
+        out.append(v[off : off + a.size].reshape(a.shape))
+        off += a.size
+    return out if many else out[0]
+
+
 class _Bucket:
     """Owner of one flat byte buffer (1-D uint8, C-contiguous, writable)."""
 
