@@ -347,7 +347,8 @@ int fedagg_lockstep_execute(fedagg_comm* comm, const fedagg_lockstep_run* runs, 
  * kernels.  Each run's chain kernel writes its accumulator straight into the consumer's slot (or
  * the root's output) through an IPC mapping over xGMI, continuing the input accumulator it reads
  * from this rank's own slot (fedagg_fedavg_chain_push_{f32,bf16}, fedagg_scaffold_chain_push_*).  Cross-process
- * order: one monotonic progress counter per rank in a node-shared host page; a call publishes
+ * order: one monotonic progress counter per rank in a page of rank 0's uncached device memory
+ * that every rank maps (fedagg_ipc_open) and the hosts read with fedagg_device_read; a call publishes
  * base + 1 on entry (the rank's earlier stream work is done: peers may write into its buffers),
  * then before step t a one-lane wait kernel polls the counters the step needs and after it a
  * one-lane signal kernel publishes base + t + 2 (system-scope release); the next call's base is
@@ -355,8 +356,8 @@ int fedagg_lockstep_execute(fedagg_comm* comm, const fedagg_lockstep_run* runs, 
  * of another rank, so no hardware-queue mapping can deadlock it; a wait that exceeds
  * `timeout_ticks` (wall-clock ticks) gives up and records the counter index + 1 in
  * progress[nranks + rank] (+ 2^32 when it was a landing tag; the host checks it).
- * Landing tags: the counters travel to host memory over PCIe while the data a step pushed travels
- * over xGMI into the consumer's HBM, so a counter is no proof that the data landed.  After step t a
+ * Landing tags: the counters travel to the page on rank 0 while the data a step pushed travels
+ * into the consumer's own HBM, so a counter is no proof that the data landed.  After step t a
  * rank's signal kernel also writes the call's generation (base + 1) into one tag word per consumer
  * it pushed to at step t -- in the consumer's own (uncached) HBM, over the same link as the data,
  * after the step's runs each ended with a system-scope release -- and a consumer waits for the tag
@@ -371,13 +372,16 @@ int fedagg_ipc_get(const void* ptr, void* handle_out, uint64_t* offset_out);
 /* map another process's allocation (hipIpcOpenMemHandle, peer access enabled lazily) */
 int fedagg_ipc_open(const void* handle, void** base_out);
 int fedagg_ipc_close(void* base);
-/* page-locked, device-mapped view of host memory (a node-shared page of progress counters) */
-int fedagg_host_map(void* host, uint64_t bytes, void** dev_out);
-int fedagg_host_unmap(void* host);
 /* device memory no L2 caches (hipDeviceMallocUncached), zeroed: the push executor's landing
- * buffers, written by peers, read by this GPU's kernels without stale cache lines */
+ * buffers and its page of progress counters, written by peers, read by this GPU's kernels without
+ * stale cache lines.  fedagg_device_free releases a block to the process, not to the runtime (a
+ * block that a kernel has read is never freed): it serves a later allocation of at most its size
+ * and more than half of it. */
 int fedagg_device_alloc_uncached(uint64_t bytes, void** out);
 int fedagg_device_free(void* p);
+/* device memory (also a peer's, mapped) copied to the host on the calling thread's own stream:
+ * ordered after no other stream's work, so it reads the progress page while kernels still poll it */
+int fedagg_device_read(void* host_dst, const void* dev_src, uint64_t bytes);
 #if FEDAGG_TUNING
 /* FEDAGG_TUNING build only (the product library does not export it): device-to-device runtime
  * copy on `stream` (the same HIP runtime as the caller's streams), for tools/push_tail_probe.py.

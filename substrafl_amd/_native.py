@@ -115,11 +115,10 @@ SIGNATURES = {
     "fedagg_ipc_get": (c_int, [c_void, c_void, P(c_u64)]),
     "fedagg_ipc_open": (c_int, [c_void, P(c_void)]),
     "fedagg_ipc_close": (c_int, [c_void]),
-    "fedagg_host_map": (c_int, [c_void, c_u64, P(c_void)]),
-    "fedagg_host_unmap": (c_int, [c_void]),
     "fedagg_wall_clock_hz": (c_int, [P(c_u64)]),
     "fedagg_device_alloc_uncached": (c_int, [c_u64, P(c_void)]),
     "fedagg_device_free": (c_int, [c_void]),
+    "fedagg_device_read": (c_int, [c_void, c_void, c_u64]),
     "fedagg_push_execute": (c_int, [c_void, c_int, c_void, c_int, c_void, c_int, c_int, c_void, c_int, c_int, c_u64,
                                     c_u64, c_void, c_void, c_u64, c_int, c_void, c_void, c_int, c_void, c_int, c_void]),
     "fedagg_session_create": (c_void, [c_int]),

@@ -24,6 +24,7 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include "fedagg.h"
@@ -164,7 +165,7 @@ int run_one(const fedagg_lockstep_run& r, hipStream_t s) {
 }
 
 
-// ---- push executor (fedagg_push_execute): progress counters in a node-shared host page ----
+// ---- push executor (fedagg_push_execute): progress counters in a page of device memory the ranks share ----
 constexpr int PUSH_MAX_WAITS = 32;  // counters / tags one wait kernel polls (one lane each)
 constexpr int PUSH_MAX_TAGS = 16;   // landing tags one signal kernel writes (one lane each)
 constexpr uint64_t PUSH_TAG_ERR = 1ull << 32;   // err word: a landing tag (not a counter) timed out
@@ -185,7 +186,7 @@ __device__ __forceinline__ uint64_t ld_acquire_sys(const uint64_t* p) {
 }
 
 // The first rank whose err word is set (its wait gave up: the call's result is void everywhere),
-// or -1.  errs: the nranks err words of the node-shared page.
+// or -1.  errs: the nranks err words of the shared page.
 __device__ __forceinline__ int push_failed_rank(const uint64_t* errs, uint32_t nranks) {
   for (uint32_t j = 0; j < nranks; ++j)
     if (ld_acquire_sys(errs + j)) return (int)j;
@@ -195,15 +196,15 @@ __device__ __forceinline__ int push_failed_rank(const uint64_t* errs, uint32_t n
 // Lane i polls progress[idx[i]] until it reaches val[i] (system-scope acquire: what the producer
 // released before its signal is visible to the kernels after this one); then, for a landing tag,
 // its tag word until it holds this call's generation `gen` -- a tag still missing when the counter
-// was already there is the ordering gap between the PCIe counter and the xGMI data: counted in
-// *late and waited out.  A wait that exceeds `timeout` ticks gives up and records idx + 1 (+
-// PUSH_TAG_ERR for a tag) in *err.  Fail fast: a wait also gives up as soon as ANY rank's err word
+// was already there is the ordering gap between the counter (in the page's memory) and the data (in
+// the consumer's): counted in *late and waited out.  A wait that exceeds `timeout` ticks gives up
+// and records idx + 1 (+ PUSH_TAG_ERR for a tag) in *err.  Fail fast: a wait also gives up as soon as ANY rank's err word
 // is set (a peer's or an earlier wait of this rank: the call's result is void), recording
 // PUSH_PEER_ERR + that rank + 1 when the cause is another rank's, so a dead or slow peer costs
 // the group one timeout, not one per wait.  The err words are scanned every PUSH_ERR_SCAN_EVERY
 // polls and not on entry (on the error-free path a wait whose counter is already there
-// reads no err word at all -- the entry scan of nranks uncached host-page words cost ~9 us per step,
-// profiles/r06f_push_overhead_probe.jsonl; a failure is still seen within tens of microseconds).
+// reads no err word at all -- the entry scan of nranks words, of a page in host memory then, cost
+// ~9 us per step, profiles/r06f_push_overhead_probe.jsonl; a failure is still seen within tens of microseconds).
 // Every lane reaches the end (the late count is a wave ballot).
 constexpr uint32_t PUSH_ERR_SCAN_EVERY = 16;
 
@@ -252,7 +253,7 @@ __global__ void __launch_bounds__(64) push_wait_kernel(const uint64_t* progress,
 // After everything before it on the stream (the step's push runs, whose peer stores are
 // system-scope write-through stores each wave waited to be acknowledged before retiring -- no
 // release fence there): the landing tags of the consumers this step pushed to (peer HBM, the
-// data's own path), then a release, then progress[idx] = value (the node-shared host page).
+// data's own path), then a release, then progress[idx] = value (the shared page).
 __global__ void __launch_bounds__(64) push_signal_kernel(uint64_t* progress, uint32_t idx, uint64_t value,
                                                          PushSignalArgs t, uint64_t gen) {
   const uint32_t i = threadIdx.x;
@@ -326,6 +327,17 @@ int push_waits(const fedagg_push_wait* waits, int& wi, int nwaits, int step, uin
   }
   return FEDAGG_OK;
 }
+
+// Uncached device memory is never handed back to the runtime: freeing a block that a kernel has
+// read is not safe on every machine this runs on, so a released block stays in the process and
+// serves the next allocation of about its size (a push program's buffers repeat call after call).
+struct UncachedBlock {
+  int device;
+  uint64_t bytes;
+  bool live;
+};
+std::mutex g_uncached_mu;
+std::unordered_map<void*, UncachedBlock> g_uncached;
 
 }  // namespace
 
@@ -495,24 +507,57 @@ int fedagg_ipc_open(const void* handle, void** base_out) {
 
 int fedagg_ipc_close(void* base) { return base ? hip_check(hipIpcCloseMemHandle(base), "hipIpcCloseMemHandle") : 0; }
 
-int fedagg_host_map(void* host, uint64_t bytes, void** dev_out) {
-  if (!host || !bytes || !dev_out) return lfail(FEDAGG_EINVAL, "fedagg_host_map: invalid argument");
-  int rc;
-  if ((rc = hip_check(hipHostRegister(host, bytes, hipHostRegisterMapped), "hipHostRegister"))) return rc;
-  return hip_check(hipHostGetDevicePointer(dev_out, host, 0), "hipHostGetDevicePointer");
-}
-
-int fedagg_host_unmap(void* host) { return host ? hip_check(hipHostUnregister(host), "hipHostUnregister") : 0; }
-
 int fedagg_device_alloc_uncached(uint64_t bytes, void** out) {
   if (!out || !bytes) return lfail(FEDAGG_EINVAL, "fedagg_device_alloc_uncached: invalid argument");
   *out = nullptr;
-  int rc;
-  if ((rc = hip_check(hipExtMallocWithFlags(out, bytes, hipDeviceMallocUncached), "hipExtMallocWithFlags"))) return rc;
-  return hip_check(hipMemset(*out, 0, bytes), "hipMemset");
+  int dev = 0, rc;
+  if ((rc = hip_check(hipGetDevice(&dev), "hipGetDevice"))) return rc;
+  void* p = nullptr;
+  {  // the smallest released block of this device that fits without wasting more than it holds
+    std::lock_guard<std::mutex> lk(g_uncached_mu);
+    UncachedBlock* best = nullptr;
+    for (auto& kv : g_uncached) {
+      UncachedBlock& b = kv.second;
+      if (!b.live && b.device == dev && b.bytes >= bytes && b.bytes / 2 <= bytes &&
+          (!best || b.bytes < best->bytes)) {
+        best = &b;
+        p = kv.first;
+      }
+    }
+    if (best) best->live = true;
+  }
+  if (!p) {
+    if ((rc = hip_check(hipExtMallocWithFlags(&p, bytes, hipDeviceMallocUncached), "hipExtMallocWithFlags"))) return rc;
+    std::lock_guard<std::mutex> lk(g_uncached_mu);
+    g_uncached[p] = UncachedBlock{dev, bytes, true};
+  }
+  if ((rc = hip_check(hipMemset(p, 0, bytes), "hipMemset"))) {
+    (void)fedagg_device_free(p);
+    return rc;
+  }
+  *out = p;
+  return FEDAGG_OK;
 }
 
-int fedagg_device_free(void* p) { return p ? hip_check(hipFree(p), "hipFree") : 0; }
+int fedagg_device_free(void* p) {
+  if (!p) return FEDAGG_OK;
+  std::lock_guard<std::mutex> lk(g_uncached_mu);
+  auto it = g_uncached.find(p);
+  if (it == g_uncached.end() || !it->second.live)
+    return lfail(FEDAGG_EINVAL, "fedagg_device_free: not a live block of fedagg_device_alloc_uncached");
+  it->second.live = false;
+  return FEDAGG_OK;
+}
+
+int fedagg_device_read(void* host_dst, const void* dev_src, uint64_t bytes) {
+  if (!bytes) return FEDAGG_OK;
+  if (!host_dst || !dev_src) return lfail(FEDAGG_EINVAL, "fedagg_device_read: NULL argument");
+  int rc;
+  if ((rc = hip_check(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, hipStreamPerThread),
+                      "hipMemcpyAsync")))
+    return rc;
+  return hip_check(hipStreamSynchronize(hipStreamPerThread), "hipStreamSynchronize");
+}
 
 #if FEDAGG_TUNING
 int fedagg_copy_async(void* dst, const void* src, uint64_t bytes, void* stream) {

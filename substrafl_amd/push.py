@@ -8,8 +8,9 @@ straight into the consumer's slot -- or, for a finished piece, into the root's o
 an IPC mapping of the peer's buffer (xGMI stores, 1/65 of the kernel's traffic at C3), continuing
 its input accumulator read from this rank's own slot (``fedagg_fedavg_chain_push_{f32,bf16}``:
 the same per-element order as the chain kernels, fed_avg.py:221-222).  Order across the processes: one monotonic
-progress counter per rank in a node-shared host page, polled before a step by a one-lane wait kernel and published by a
-one-lane signal kernel on entry to a call (``base + 1``: the rank's earlier stream work -- a
+progress counter per rank in a page of rank 0's uncached device memory that every rank maps (IPC,
+like the slots; the hosts read it with ``fedagg_device_read``), polled before a step by a one-lane
+wait kernel and published by a one-lane signal kernel on entry to a call (``base + 1``: the rank's earlier stream work -- a
 refill of its output, the previous call -- is done) and after each step t (``base + t + 2``).
 Before step t a rank waits for
 
@@ -20,8 +21,8 @@ Before step t a rank waits for
 
 after the last step the root waits for every rank's last step.
 
-A counter reaches host memory over PCIe while the data of the same step travels over xGMI into
-the consumer's HBM, so the counter alone does not prove the data landed.  Landing tags close that
+A counter reaches the page on rank 0 while the data of the same step travels into the consumer's
+own HBM, so the counter alone does not prove the data landed.  Landing tags close that
 gap: a run storing into a peer (``FEDAGG_RUN_FEDAVG_PUSH``, the Scaffold push runs) writes with
 system-scope write-through stores (``sc0 sc1``) and every wave waits for their acknowledgement
 (``s_waitcnt vmcnt(0)``) before it retires -- no L2 writeback, no release fence: the stores are
@@ -43,7 +44,7 @@ Scope: row-layout client blocks of FedAvg over fp32 (the bench's C3 schedule) or
 (C5; fp32 accumulators), and of Scaffold over fp32 or fp64 buckets (fp64 accumulators: each run is
 two launches, the delta bucket and the control-variate bucket, ``fedagg_scaffold_chain_push_*``,
 scaffold.py:262-263, 293); FedAvg's fp64 / fp16 kinds keep the RCCL executor.  Every rank must be
-on this node (the counters live in ``/dev/shm``).
+on this node (the counters, like the slots, are shared through IPC mappings).
 """
 
 from __future__ import annotations
@@ -118,27 +119,30 @@ class PushTransport:
         lands, the proof of it never does)."""
         import torch
         import torch.distributed as dist
-        from multiprocessing import shared_memory
 
         self.lib = _native.load()
         self.dist, self.group = dist, group
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self.device = torch.cuda.current_device() if device is None else int(device)
-        # counters [0, G), wait errors [G, 2G), late landing tags [2G, 3G)
+        # counters [0, G), wait errors [G, 2G), late landing tags [2G, 3G): a zeroed page of rank 0's
+        # uncached device memory, mapped by the other ranks; _page is the host's snapshot of it
         nbytes = PAGE * max(1, -(-(3 * self.world * 8) // PAGE))
-        name = [None]
+        self._page_u = self._page_base = None
+        info = [None]
         if self.rank == 0:
-            self._shm = shared_memory.SharedMemory(create=True, size=nbytes)
-            self._shm.buf[:nbytes] = bytes(nbytes)
-            name = [self._shm.name]
+            self._page_u = _Uncached(self.lib, nbytes)
+            self._dev = self._page_u.ptr
+            if self.world > 1:
+                info = [self.ipc_info(self._dev)]
         self._src0 = 0 if group is None else dist.get_global_rank(group, 0)
-        dist.broadcast_object_list(name, src=self._src0, group=group)
+        dist.broadcast_object_list(info, src=self._src0, group=group)
         if self.rank != 0:
-            self._shm = shared_memory.SharedMemory(name=name[0])
-        self._page = np.frombuffer(self._shm.buf, dtype=np.uint64, count=nbytes // 8)
-        dev = ctypes.c_void_p()
-        _check(self.lib.fedagg_host_map(self._page.ctypes.data, nbytes, ctypes.byref(dev)), "fedagg_host_map")
-        self._dev = dev.value
+            base = ctypes.c_void_p()
+            buf = (ctypes.c_char * len(info[0][0])).from_buffer_copy(info[0][0])
+            _check(self.lib.fedagg_ipc_open(buf, ctypes.byref(base)), "fedagg_ipc_open")
+            self._page_base = int(base.value)  # not in _maps: it lives as long as the transport
+            self._dev = self._page_base + info[0][1]
+        self._page = np.zeros(3 * self.world, dtype=np.uint64)
         hz = ctypes.c_uint64()
         _check(self.lib.fedagg_wall_clock_hz(ctypes.byref(hz)), "fedagg_wall_clock_hz")
         self._timeout = int(timeout_s * hz.value)
@@ -178,8 +182,8 @@ class PushTransport:
         return self._maps[h] + off
 
     def release_programs(self) -> None:
-        """Free every compiled program: its uncached slots / landing / tag / staging buffers and the
-        IPC mappings of the peers' ones.  Collective (every rank at once): this rank's stream is
+        """Release every compiled program: its uncached slots / landing / tag / staging buffers (kept
+        for the next program's) and the IPC mappings of the peers' ones.  Collective (every rank at once): this rank's stream is
         synchronised and the group meets first, so no rank's kernels still read or write what goes
         away.  Without it each call with new client blocks (the host entry points) would keep a
         program -- and every peer's mappings of its buffers -- alive."""
@@ -225,16 +229,24 @@ class PushTransport:
             self._py = DistTransport(self.group)
         return self._py
 
+    def _read_page(self) -> np.ndarray:
+        """The shared page as it is now, copied into ``_page`` (on a stream of its own: behind no
+        kernel that still polls the page)."""
+        if getattr(self, "_dev", None):  # no device page: _page itself is the record
+            _check(self.lib.fedagg_device_read(self._page.ctypes.data, self._dev, self._page.nbytes),
+                   "fedagg_device_read")
+        return self._page
+
     def errors(self) -> Dict[int, str]:
         """Ranks whose wait kernel gave up: rank -> what it waited for (a rank's progress counter,
         or the landing tag of a rank's push), or which rank's failure it stopped waiting after."""
-        e = self._page[self.world: 2 * self.world]
+        e = self._read_page()[self.world: 2 * self.world]
         return {r: _describe_wait_error(int(v)) for r, v in enumerate(e) if v}
 
     def late_tags(self) -> List[int]:
         """Per rank: landing-tag waits that found the producer's counter published but its data's
-        tag not yet landed (the PCIe-counter / xGMI-data ordering gap, waited out), cumulative."""
-        return [int(v) for v in self._page[2 * self.world: 3 * self.world]]
+        tag not yet landed (the counter / data ordering gap, waited out), cumulative."""
+        return [int(v) for v in self._read_page()[2 * self.world: 3 * self.world]]
 
     # -- the schedule ----------------------------------------------------------------------
     def program(self, **kw) -> "PushProgram":
@@ -318,7 +330,7 @@ class PushTransport:
         if self._page is None or self.world == 1:
             return
         deadline = time.monotonic() + self._timeout_s + 5.0
-        while not self.errors():
+        while not self.errors():  # reads the page: the counters below are of the same snapshot
             if all(int(v) >= self.base for v in self._page[: self.world]):
                 return
             if time.monotonic() > deadline:
@@ -346,22 +358,23 @@ class PushTransport:
         torch.cuda.synchronize(self.device)
         if self.failed():  # no barrier a dead peer would never meet
             self._abandon_programs()
+            if self._page_u is not None:
+                _ABANDONED.append(self._page_u)  # a surviving peer may still poll the page
         else:
             self.dist.barrier(group=self.group)  # nobody writes into a mapping that is going away
         self._programs.clear()
         for base in self._maps.values():
             self.lib.fedagg_ipc_close(base)
         self._maps.clear()
-        self.lib.fedagg_host_unmap(self._page.ctypes.data)
+        if self._page_base is not None:
+            self.lib.fedagg_ipc_close(self._page_base)
+        self._page_u = self._page_base = None
         self._dev = None
         self._page = None
-        self._shm.close()
-        if self.rank == 0:
-            self._shm.unlink()
 
 
 FAULT_EXIT_CODE = 17  # TEST ONLY: the exit status of a rank the ("exit", rank, t) fault kills
-_ABANDONED: List["PushProgram"] = []  # programs of failed transports: never freed while the process lives
+_ABANDONED: list = []  # programs and pages of failed transports: never released while the process lives
 
 PUSH_TAG_ERR, PUSH_PEER_ERR = 1 << 32, 1 << 33  # csrc/lockstep.hip: the err word's cause bits
 
@@ -388,7 +401,8 @@ def _hw_queues() -> int:
 
 
 class _Uncached:
-    """Device memory no L2 caches (fedagg_device_alloc_uncached), freed with its owner."""
+    """Device memory no L2 caches (fedagg_device_alloc_uncached), zeroed; released with its owner
+    for the next allocation of its size (never handed back to the runtime)."""
 
     def __init__(self, lib, nbytes: int):
         self.lib, self.bytes = lib, int(nbytes)

@@ -298,6 +298,48 @@ def test_scaffold_push_run_continues_its_input_accumulator(kind, K, M, finish):
         assert torch.equal(got[1].view(torch.int64), ref_c.view(torch.int64)), (seed, "control variate")
 
 
+def test_uncached_blocks_are_reused_zeroed_and_read_back():
+    """fedagg_device_alloc_uncached / _free / _read: a released block serves the next allocation of
+    at most its size and more than half of it, zeroed again (it is never handed back to the
+    runtime); a pointer that is no live block is refused; fedagg_device_read copies to the host."""
+    import ctypes
+
+    import torch
+
+    from substrafl_amd import _native
+
+    lib = _native.load()
+    torch.cuda.set_device(0)
+
+    def alloc(n):
+        p = ctypes.c_void_p()
+        assert lib.fedagg_device_alloc_uncached(n, ctypes.byref(p)) == 0
+        return p.value
+
+    def read(p, n):
+        host = np.full(n // 8, 7, dtype=np.uint64)
+        assert lib.fedagg_device_read(host.ctypes.data, p, n) == 0
+        return host
+
+    n = 12_345 * 8  # a size no other test of this process leaves in the pool
+    a = alloc(n)
+    assert not read(a, n).any()
+    src = torch.arange(1, n // 4 + 1, dtype=torch.float32, device="cuda")  # one client, weight 1: a copy
+    _native.check(lib.fedagg_fedavg_chain_f32(_native.ptr_array([src.data_ptr()]), (ctypes.c_float * 1)(1.0), 1,
+                                              n // 4, 1, a, torch.cuda.current_stream().cuda_stream), "chain")
+    torch.cuda.synchronize()
+    assert np.array_equal(read(a, n).view(np.float32), np.arange(1, n // 4 + 1, dtype=np.float32))
+    b = alloc(n)  # a is live: a block of its own
+    assert b != a
+    assert lib.fedagg_device_free(a) == 0
+    assert lib.fedagg_device_free(a) != 0 and lib.fedagg_device_free(a + 8) != 0  # not live / not a block
+    d = alloc(n // 2 - 8)
+    assert d not in (a, b)  # less than half of a: a is left for a larger request
+    c = alloc(n - 64)
+    assert c == a and not read(c, n - 64).any()  # reused, and zeroed again
+    assert all(lib.fedagg_device_free(p) == 0 for p in (b, c, d))
+
+
 # ---------------------------------------------------------------------------- the failure path
 FAULT_TIMEOUT_S = 3.0
 FAULT_SHAPES = [(37, 29), (1,), (3_000_000,), (1, 1)]  # 2-3 relay chunks: several steps

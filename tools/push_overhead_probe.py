@@ -5,7 +5,7 @@ the step's signal kernel writing ``--waits`` tags; and the same S steps around t
 64-client x n-element block (runs alone, through the executor's own run table, against runs +
 waits + signals).  Also the cost of the push runs' per-wave system-scope release
 (``fedagg_fedavg_chain_push_f32`` against ``fedagg_fedavg_chain_f32``, back to back).  The counters
-live in a page-locked host page, as in substrafl_amd/push.py.
+live in device memory, as in substrafl_amd/push.py (there uncached, here a torch tensor).
 
   python tools/push_overhead_probe.py [--steps 48] [--n 2600000] [--waits 6] [--push-runs]
 """
@@ -39,9 +39,8 @@ def main():
     torch.cuda.set_device(0)
     lib = _native.load()
     G = max(2, a.waits + 1)
-    page = np.zeros(512, np.uint64)
-    dev = ctypes.c_void_p()
-    push._check(lib.fedagg_host_map(page.ctypes.data, page.nbytes, ctypes.byref(dev)), "fedagg_host_map")
+    page = torch.zeros(512, dtype=torch.int64, device="cuda")
+    dev = ctypes.c_void_p(page.data_ptr())
     page[1:G] = 1 << 40  # the other "ranks" are far ahead: every wait is satisfied at once
     K, n, S = a.clients, a.n, a.steps
     rows = torch.randn((K, n), dtype=torch.float32, device="cuda")
@@ -123,7 +122,6 @@ def main():
                       "runs_only_ms": round(runs_only, 4), "order_only_ms": round(order, 4), "order_us_per_step": round(order / S * 1e3, 2),
                       "runs_and_signals_ms": round(runs_sig, 4), "runs_signals_waits_ms": round(both, 4),
                       "added_us_per_step": round((both - runs_only) / S * 1e3, 2)}), flush=True)
-    lib.fedagg_host_unmap(page.ctypes.data)
 
 
 if __name__ == "__main__":
