@@ -69,8 +69,51 @@ def _reference_base(algo_cls):
 
 def _export(self, tensors, tag="export"):
     if getattr(self, "_fedagg_mxfp8", False):
-        return wm.export_mxfp8(tensors, tag=tag)
+        residual = _mx_residual(self, tensors) if getattr(self, "_fedagg_error_feedback", False) else None
+        return wm.export_mxfp8(tensors, tag=tag, residual=residual)
     return wm.export_numpy(tensors, wire=self._fedagg_wire, tag=tag)
+
+
+def _mx_residual(self, tensors):
+    """The client's error-feedback residual for the bucket ``tensors``: ``None`` until the first
+    ``train``, then fp32 zeros of the bucket's size on its device (fp32 for a bf16 model too), which
+    every export updates in place.  A bucket of another size is a ``ValueError``."""
+    import torch
+
+    M = sum(t.numel() for t in tensors)
+    res = self._fedagg_mx_residual
+    if res is None:
+        res = torch.zeros(M, dtype=torch.float32, device=tensors[0].device)
+    elif res.numel() != M:
+        raise ValueError(f"error_feedback: the residual holds {res.numel()} elements, the update {M}: "
+                         "the model's parameters changed between rounds")
+    elif res.device != tensors[0].device:  # a checkpoint restored elsewhere
+        res = res.to(tensors[0].device)
+    self._fedagg_mx_residual = res
+    return res
+
+
+def _checkpoint_methods():
+    """``_get_state_to_save`` / ``_update_from_checkpoint`` of an error-feedback class, and the cell
+    that takes the class once it exists (what the two hand to ``super()``).  In remote and docker
+    mode every task is its own process and the algo travels through ``save_local_state`` /
+    ``load_local_state``: without these the residual would be lost every round."""
+    cell = []
+
+    def _get_state_to_save(self):
+        """The base's checkpoint (torch_base_algo.py:287-350) plus the residual (a tensor or None)."""
+        state = super(cell[0], self)._get_state_to_save()
+        state["fedagg_mx_residual"] = self._fedagg_mx_residual
+        return state
+
+    def _update_from_checkpoint(self, path):
+        """The base's restore, then the residual popped: ``load_local_state`` asserts that the
+        checkpoint is empty afterwards (torch_base_algo.py:284)."""
+        checkpoint = super(cell[0], self)._update_from_checkpoint(path=path)
+        self._fedagg_mx_residual = checkpoint.pop("fedagg_mx_residual")
+        return checkpoint
+
+    return cell, _get_state_to_save, _update_from_checkpoint
 
 
 def _fedavg_train(shared_state_cls):
@@ -258,7 +301,7 @@ def _registering_init(base_init):
     return __init__
 
 
-def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
+def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feedback: bool = False):
     """A subclass of ``algo_cls`` (SubstraFL's ``TorchFedAvgAlgo`` / ``TorchScaffoldAlgo`` /
     ``TorchNewtonRaphsonAlgo`` or a subclass of one) whose ``train`` moves weights with the
     flat-bucket kernels.  ``wire``: ``True`` exports :class:`..wire.BucketArray` layers instead of plain
@@ -266,7 +309,12 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
     ``ValueError``) quantises the update of an fp32 or bf16 model on the device to OCP MXFP8
     (:func:`.weight_manager.export_mxfp8`: 1.03 bytes per parameter in one buffer; the aggregator's
     fp32 average comes back and is applied by the existing paths; no error feedback or residual
-    is carried between rounds).  ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
+    is carried between rounds unless ``error_feedback=True``).  ``error_feedback`` (only with
+    ``wire="mxfp8"``; a ``TypeError`` otherwise): the client keeps what the quantiser dropped, an fp32
+    residual of 4 bytes per parameter in ``_fedagg_mx_residual`` (device memory, and the checkpoint
+    key ``"fedagg_mx_residual"``), and adds it to the next round's update before quantising, in one
+    fused kernel (``libfedagg_mxef.so``, include/fedagg_mxef.h); the wire format does not change.
+    ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
     default, keeps the reference's eigenvalue check and never loads the dense library;
     ``"device"`` tries a Cholesky certificate on the GPU first
     (:func:`..integration.newton_raphson_hessian_check`; ``FEDAGG_NR_CHECK`` overrides it when
@@ -278,6 +326,9 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
     mxfp8 = wire == "mxfp8"
     if mxfp8 and kind != "fedavg":
         raise TypeError(f"wire='mxfp8' is an option of TorchFedAvgAlgo, not of {base.__name__}")
+    if error_feedback and not mxfp8:
+        raise TypeError(f"error_feedback is an option of wire='mxfp8' (TorchFedAvgAlgo), not of wire={wire!r} on "
+                        f"{base.__name__}")
     if kind != "newton_raphson" and hessian_check is not None:
         raise TypeError(f"hessian_check is an option of TorchNewtonRaphsonAlgo, not of {base.__name__}")
     if kind == "newton_raphson" and hessian_check not in (None, "host", "device"):
@@ -304,7 +355,13 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None):
         ns["_scaffold_parameters_update"] = _scaffold_parameters_update
     else:
         ns["train"] = remote_data(_fedavg_train(schemas.FedAvgSharedState))
+    if error_feedback:  # only then: every other class stays attribute for attribute what it is
+        cell, get_state, update_from = _checkpoint_methods()
+        ns.update({"_fedagg_error_feedback": True, "_fedagg_mx_residual": None,
+                   "_get_state_to_save": get_state, "_update_from_checkpoint": update_from})
     cls = type(algo_cls.__name__, (algo_cls,), ns)
+    if error_feedback:
+        cell.append(cls)
     # not importable by name: cloudpickle carries the class by value into the task process
     cls.__qualname__ = f"accelerate_algo.<locals>.{algo_cls.__name__}"
     return cls

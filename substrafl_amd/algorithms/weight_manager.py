@@ -370,7 +370,8 @@ def _host_array(t: torch.Tensor) -> np.ndarray:
     return t.numpy()
 
 
-def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export") -> List[np.ndarray]:
+def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export", residual: Optional[torch.Tensor] = None
+                 ) -> List[np.ndarray]:
     """The MXFP8 form of ``tensors`` (``wire.py``: L ``wire.E4M3`` layers, then one ``wire.E8M0``
     scale array over the raveled concatenation), quantised on the device by
     ``fedagg_mx_quantize`` from the flat fp32 or bf16 bucket.  Codes and scales share one device
@@ -378,7 +379,13 @@ def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export") -> List[n
     buffer, and the layers returned are :class:`wire.BucketArray` views of it: they pickle as that
     one buffer.  Anything but fp32 or bf16 tensors on a ROCm device is refused
     (``NotImplementedError``): there is no host quantiser behind this and the fp32 average could
-    not go back onto an fp16 or fp64 model through the flat kernels."""
+    not go back onto an fp16 or fp64 model through the flat kernels.
+
+    ``residual`` (error feedback): a contiguous fp32 tensor of M elements on the bucket's device.
+    ``fedagg_mxef_quantize`` (``libfedagg_mxef.so``, loaded only here) then encodes
+    ``fl32(x + residual)`` and overwrites ``residual`` with what the encoding dropped, in the same
+    single pass; any other dtype, device, layout or size is a ``ValueError`` before any device work.
+    Everything after the kernel is the same."""
     from .. import _native_mx, runtime
     from ..wire import E4M3, E8M0, MX_BLOCK
 
@@ -388,13 +395,27 @@ def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export") -> List[n
         dts = sorted({str(t.dtype) for t in tensors})
         raise NotImplementedError(f"wire='mxfp8': the update of an fp32 or bf16 model on a ROCm device is quantised, "
                                   f"got {dts} on {sorted({str(t.device) for t in tensors})}")
+    M = sum(t.numel() for t in tensors)
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32 or not residual.is_contiguous():
+            raise ValueError("export_mxfp8: residual must be a contiguous float32 tensor, got "
+                             f"{getattr(residual, 'dtype', type(residual).__name__)}")
+        if residual.device != tensors[0].device:
+            raise ValueError(f"export_mxfp8: residual is on {residual.device}, the bucket on {tensors[0].device}")
+        if residual.numel() != M:
+            raise ValueError(f"export_mxfp8: residual holds {residual.numel()} elements, the bucket {M}")
     flat = flat_bucket(tensors)
     if flat is None:
         flat = _gather_flat(tensors)
-    M = flat.numel()
     n_scales = -(-M // MX_BLOCK)
     dev = torch.empty(M + n_scales, dtype=torch.uint8, device=flat.device)
-    _native_mx.quantize(flat.data_ptr(), kind, M, dev.data_ptr(), dev.data_ptr() + M, _stream(flat.device))
+    if residual is None:
+        _native_mx.quantize(flat.data_ptr(), kind, M, dev.data_ptr(), dev.data_ptr() + M, _stream(flat.device))
+    else:
+        from .. import _native_mxef
+
+        _native_mxef.quantize_ef(flat.data_ptr(), kind, M, residual.data_ptr(), dev.data_ptr(), dev.data_ptr() + M,
+                                 _stream(flat.device))
     host = runtime.reusable_host_array(M + n_scales, np.dtype(np.uint8), tag)
     torch.cuda.current_stream(flat.device).synchronize()  # the quantiser ran on torch's stream
     with runtime.device_lock(flat.device.index):  # the session's ring is shared with the engine
