@@ -1,7 +1,7 @@
-"""Build hook of the installable package (pyproject.toml): ``build_py`` also compiles
-``libfedagg.so``, ``libfedagg_dense.so``, ``libfedagg_promote.so``, ``libfedagg_mx.so`` and ``libfedagg_mxef.so`` for gfx950 into the build tree with the same compiler, flags and object cache as
-``__graft_entry__.build()``, so the wheel carries the HIP library next to the Python package.
-No hipcc, no wheel: ``compile_library`` raises, and the build fails loudly."""
+"""Build hook of the installable package (pyproject.toml): ``build_py`` also compiles every library of
+``__graft_entry__.LIBRARIES`` for gfx950 into the build tree with the same compiler, flags and object cache as
+``__graft_entry__.build()``, so the wheel carries the HIP libraries next to the Python package.
+No hipcc, no wheel: ``compile_entry`` raises, and the build fails loudly."""
 
 import sys
 from pathlib import Path
@@ -20,11 +20,8 @@ class BuildPyWithHip(build_py):
         import __graft_entry__
 
         pkg = Path(self.build_lib).resolve() / "substrafl_amd"
-        __graft_entry__.compile_library(pkg / "libfedagg.so")
-        __graft_entry__.compile_dense_library(pkg / "libfedagg_dense.so")
-        __graft_entry__.compile_promote_library(pkg / "libfedagg_promote.so")
-        __graft_entry__.compile_mx_library(pkg / "libfedagg_mx.so")
-        __graft_entry__.compile_mxef_library(pkg / "libfedagg_mxef.so")
+        for lib in __graft_entry__.LIBRARIES:
+            __graft_entry__.compile_entry(lib, pkg / lib.name)
 
 
 class BinaryDistribution(Distribution):

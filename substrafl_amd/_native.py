@@ -9,12 +9,10 @@ the CPU or through another backend.
 from __future__ import annotations
 
 import ctypes
-import os
-from pathlib import Path
-from typing import Optional
 
-_HERE = Path(__file__).resolve().parent
-LIB_PATH = Path(os.environ.get("FEDAGG_LIB", str(_HERE / "libfedagg.so")))
+from ._loader import Library, NativeLibraryError, lib_path  # noqa: F401  (NativeLibraryError: this module's to export)
+
+LIB_PATH = lib_path("FEDAGG_LIB", "libfedagg.so")
 
 c_u64 = ctypes.c_uint64
 c_i64 = ctypes.c_int64
@@ -190,44 +188,9 @@ FEDAGG_RUN_FEDAVG, FEDAGG_RUN_FEDAVG_TILED, FEDAGG_RUN_SCAFFOLD, FEDAGG_RUN_FEDA
 FEDAGG_RUN_SCAFFOLD_PUSH_DELTA, FEDAGG_RUN_SCAFFOLD_PUSH_CV = 4, 5
 
 
-class NativeLibraryError(RuntimeError):
-    """libfedagg.so is missing, failed to load, or a call returned an error code."""
-
-
-_lib: Optional[ctypes.CDLL] = None
-
-
-def load() -> ctypes.CDLL:
-    """Load (once) and return the native library; raise loudly if it is not there."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise NativeLibraryError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The aggregation engine has no CPU fallback."
-        )
-    try:
-        lib = ctypes.CDLL(str(LIB_PATH))
-    except OSError as e:  # pragma: no cover - depends on the box
-        raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    sigs = dict(SIGNATURES)
-    if lib.fedagg_tuning_build():
-        sigs.update(TUNING_SIGNATURES)
-    for name, (res, args) in sigs.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fedagg_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfedagg ABI version mismatch")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().fedagg_last_error().decode(errors="replace")
-        raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
+_library = Library(globals(), "fedagg_", "The aggregation engine has no CPU fallback.",
+                   more_signatures=lambda lib: TUNING_SIGNATURES if lib.fedagg_tuning_build() else {})
+load, check = _library.load, _library.check
 
 
 def ptr_array(ptrs) -> ctypes.Array:

@@ -10,19 +10,11 @@ library raises :class:`substrafl_amd._native.NativeLibraryError`.
 from __future__ import annotations
 
 import ctypes
-import os
-from pathlib import Path
-from typing import Optional
 
-from ._native import NativeLibraryError
+from ._loader import Library, lib_path
+from ._native import P, c_int, c_u64, c_void
 
-_HERE = Path(__file__).resolve().parent
-LIB_PATH = Path(os.environ.get("FEDAGG_DENSE_LIB", str(_HERE / "libfedagg_dense.so")))
-
-c_u64 = ctypes.c_uint64
-c_int = ctypes.c_int
-c_void = ctypes.c_void_p
-P = ctypes.POINTER
+LIB_PATH = lib_path("FEDAGG_DENSE_LIB", "libfedagg_dense.so")
 
 # Every symbol include/fedagg_dense.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -44,42 +36,9 @@ SIGNATURES = {
 
 ABI_VERSION = 1
 
-_lib: Optional[ctypes.CDLL] = None
-
-
-def loaded() -> bool:
-    """Whether this process has loaded the dense library (the default paths never do)."""
-    return _lib is not None
-
-
-def load() -> ctypes.CDLL:
-    """Load (once) and return the dense library; raise loudly if it is not there."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise NativeLibraryError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The device solve has no CPU fallback; solve='host' needs no library."
-        )
-    try:
-        lib = ctypes.CDLL(str(LIB_PATH))
-    except OSError as e:  # pragma: no cover - depends on the box
-        raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fedagg_dense_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfedagg_dense ABI version mismatch")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().fedagg_dense_last_error().decode(errors="replace")
-        raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
+_library = Library(globals(), "fedagg_dense_",
+                   "The device solve has no CPU fallback; solve='host' needs no library.")
+load, loaded, check = _library.load, _library.loaded, _library.check  # loaded(): the default paths never load it
 
 
 def call(name: str, *args) -> None:

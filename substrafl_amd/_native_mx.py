@@ -12,19 +12,12 @@ copy of the library.
 from __future__ import annotations
 
 import ctypes
-import os
-from pathlib import Path
-from typing import Optional, Tuple
+from typing import Tuple
 
-from ._native import NativeLibraryError
+from ._loader import Library, lib_path
+from ._native import P, c_int, c_u64, c_void, ptr_array
 
-_HERE = Path(__file__).resolve().parent
-LIB_PATH = Path(os.environ.get("FEDAGG_MX_LIB", str(_HERE / "libfedagg_mx.so")))
-
-c_u64 = ctypes.c_uint64
-c_int = ctypes.c_int
-c_void = ctypes.c_void_p
-P = ctypes.POINTER
+LIB_PATH = lib_path("FEDAGG_MX_LIB", "libfedagg_mx.so")
 
 # Every symbol include/fedagg_mx.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -40,42 +33,8 @@ ABI_VERSION = 1
 MX_BLOCK = 32  # FEDAGG_MX_BLOCK
 MAX_PAIRWISE_K = 256  # FEDAGG_MX_MAX_PAIRWISE_K
 
-_lib: Optional[ctypes.CDLL] = None
-
-
-def loaded() -> bool:
-    """Whether this process has loaded the library (only an MXFP8 call does)."""
-    return _lib is not None
-
-
-def load() -> ctypes.CDLL:
-    """Load (once) and return the library; raise loudly if it is not there."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise NativeLibraryError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The MXFP8 wire has no fallback."
-        )
-    try:
-        lib = ctypes.CDLL(str(LIB_PATH))
-    except OSError as e:  # pragma: no cover - depends on the box
-        raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fedagg_mx_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfedagg_mx ABI version mismatch")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().fedagg_mx_last_error().decode(errors="replace")
-        raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
+_library = Library(globals(), "fedagg_mx_", "The MXFP8 wire has no fallback.")
+load, loaded, check = _library.load, _library.loaded, _library.check  # loaded(): only an MXFP8 call loads it
 
 
 def blocking() -> Tuple[int, int]:
@@ -88,8 +47,6 @@ def blocking() -> Tuple[int, int]:
 def fedavg_e4m3(code_ptrs, scale_ptrs, weights, M: int, pairwise_idx, d_out: int, stream: int) -> None:
     """``fedagg_mx_fedavg_e4m3`` over K device rows (lists of device addresses), fp32 ``weights``,
     the flat indices of the numel == 1 elements, into the fp32 device buffer ``d_out``."""
-    from ._native import ptr_array
-
     K = len(code_ptrs)
     w = (ctypes.c_float * max(1, K))(*[float(v) for v in weights])
     idx = [int(v) for v in (pairwise_idx if pairwise_idx is not None else [])]

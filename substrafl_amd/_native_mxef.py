@@ -13,19 +13,12 @@ library.
 from __future__ import annotations
 
 import ctypes
-import os
-from pathlib import Path
-from typing import Optional, Tuple
+from typing import Tuple
 
-from ._native import NativeLibraryError
+from ._loader import Library, lib_path
+from ._native import P, c_int, c_u64, c_void
 
-_HERE = Path(__file__).resolve().parent
-LIB_PATH = Path(os.environ.get("FEDAGG_MXEF_LIB", str(_HERE / "libfedagg_mxef.so")))
-
-c_u64 = ctypes.c_uint64
-c_int = ctypes.c_int
-c_void = ctypes.c_void_p
-P = ctypes.POINTER
+LIB_PATH = lib_path("FEDAGG_MXEF_LIB", "libfedagg_mxef.so")
 
 # Every symbol include/fedagg_mxef.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -37,42 +30,8 @@ SIGNATURES = {
 
 ABI_VERSION = 1
 
-_lib: Optional[ctypes.CDLL] = None
-
-
-def loaded() -> bool:
-    """Whether this process has loaded the library (only an export with a residual does)."""
-    return _lib is not None
-
-
-def load() -> ctypes.CDLL:
-    """Load (once) and return the library; raise loudly if it is not there."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise NativeLibraryError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). Error feedback on the MXFP8 wire has no fallback."
-        )
-    try:
-        lib = ctypes.CDLL(str(LIB_PATH))
-    except OSError as e:  # pragma: no cover - depends on the box
-        raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fedagg_mxef_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfedagg_mxef ABI version mismatch")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().fedagg_mxef_last_error().decode(errors="replace")
-        raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
+_library = Library(globals(), "fedagg_mxef_", "Error feedback on the MXFP8 wire has no fallback.")
+load, loaded, check = _library.load, _library.loaded, _library.check  # loaded(): only an export with a residual loads it
 
 
 def blocking() -> Tuple[int, int, int]:

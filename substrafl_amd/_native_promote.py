@@ -13,18 +13,11 @@ from __future__ import annotations
 
 import ctypes
 import os
-from pathlib import Path
-from typing import Optional
 
-from ._native import NativeLibraryError
+from ._loader import Library, lib_path
+from ._native import P, c_int, c_u64, c_void
 
-_HERE = Path(__file__).resolve().parent
-LIB_PATH = Path(os.environ.get("FEDAGG_PROMOTE_LIB", str(_HERE / "libfedagg_promote.so")))
-
-c_u64 = ctypes.c_uint64
-c_int = ctypes.c_int
-c_void = ctypes.c_void_p
-P = ctypes.POINTER
+LIB_PATH = lib_path("FEDAGG_PROMOTE_LIB", "libfedagg_promote.so")
 
 # Every symbol include/fedagg_promote.h declares, with its ctypes signature.
 SIGNATURES = {
@@ -37,49 +30,16 @@ SIGNATURES = {
 
 ABI_VERSION = 1
 
-_lib: Optional[ctypes.CDLL] = None
+_library = Library(globals(), "fedagg_promote_",
+                   "The promoted flat ops have no fallback; FEDAGG_FLAT_PROMOTE=0 "
+                   "keeps a 16-bit model's fp64 operands on the torch loops.")
+load, loaded, check = _library.load, _library.loaded, _library.check  # loaded(): fp32 models and CPU tensors never
 
 
 def enabled() -> bool:
     """Whether ``weight_manager`` sends 16-bit-next-to-fp64 operand sets to this library
     (``FEDAGG_FLAT_PROMOTE=0``: they stay on the torch loops).  Read at every call."""
     return os.environ.get("FEDAGG_FLAT_PROMOTE", "1") != "0"
-
-
-def loaded() -> bool:
-    """Whether this process has loaded the library (fp32 models and CPU tensors never do)."""
-    return _lib is not None
-
-
-def load() -> ctypes.CDLL:
-    """Load (once) and return the library; raise loudly if it is not there."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not LIB_PATH.exists():
-        raise NativeLibraryError(
-            f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The promoted flat ops have no fallback; FEDAGG_FLAT_PROMOTE=0 "
-            "keeps a 16-bit model's fp64 operands on the torch loops."
-        )
-    try:
-        lib = ctypes.CDLL(str(LIB_PATH))
-    except OSError as e:  # pragma: no cover - depends on the box
-        raise NativeLibraryError(f"cannot load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    if lib.fedagg_promote_abi_version() != ABI_VERSION:
-        raise NativeLibraryError("libfedagg_promote ABI version mismatch")
-    _lib = lib
-    return lib
-
-
-def check(rc: int, what: str) -> None:
-    if rc != 0:
-        msg = load().fedagg_promote_last_error().decode(errors="replace")
-        raise NativeLibraryError(f"{what} failed ({rc}): {msg}")
 
 
 def tune(vec: int) -> None:

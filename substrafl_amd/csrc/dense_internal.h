@@ -7,10 +7,8 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
-
 #include "fedagg_dense.h"
+#include "lib_error.h"
 
 #define DN_NB 32      // panel width; block of the triangular solves and substitutions
 #define DN_TM 64      // trailing-update tile, rows
@@ -24,22 +22,10 @@ typedef unsigned long long dn_u64;
 
 namespace fedagg_dense_detail {
 
-inline thread_local char g_error[256] = "";  // one per thread for the whole library (fedagg_dense_last_error)
-
-__attribute__((format(printf, 2, 3))) inline int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_error, sizeof(g_error), fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-inline int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return FEDAGG_DENSE_OK;
-  snprintf(g_error, sizeof(g_error), "%s: %s", what, hipGetErrorString(e));
-  return FEDAGG_DENSE_EHIP;
-}
+// one text per thread for the whole library (fedagg_dense_last_error): lib_error.h's is one object for all four sources
+using fedagg_lib_error::fail;
+using fedagg_lib_error::g_error;
+constexpr auto check_launch = fedagg_lib_error::check_launch<FEDAGG_DENSE_OK, FEDAGG_DENSE_EHIP>;
 
 // The pieces of the argument checks, before any HIP call: a pointer that must not be NULL, ...
 inline int check_ptr(const void* p, const char* name) {

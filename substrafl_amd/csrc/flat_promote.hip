@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "fedagg_promote.h"
+#include "lib_error.h"
 
 #define PR_BLOCK 256    // threads per workgroup
 #define SEG_GROUP 32    // layers per launch
@@ -23,20 +24,10 @@
 
 namespace {
 
-thread_local char g_error[256] = "";
+using fedagg_lib_error::fail;
+constexpr auto check_launch = fedagg_lib_error::check_launch<FEDAGG_OK, FEDAGG_EHIP>;
+
 std::atomic<int> g_vec{1};  // the "vec" knob
-
-int fail(int code, const char* fmt, long long v = 0) {
-  snprintf(g_error, sizeof(g_error), fmt, v);
-  return code;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return FEDAGG_OK;
-  snprintf(g_error, sizeof(g_error), "%s: %s", what, hipGetErrorString(e));
-  return FEDAGG_EHIP;
-}
 
 struct PromoteArgs {
   const void* p[FEDAGG_FLAT_MAX_LISTS][SEG_GROUP];  // list-major layer pointers
@@ -276,7 +267,7 @@ using Kernel = void (*)(const PromoteArgs, double*);
 // ptrs is list-major [nlists][L]; f64 bit j: list j is fp64, else 16-bit
 int promote_launch(Kernel kernel, const void* const* ptrs, uint32_t f64, int nlists,
                    const double* coeffs, const uint64_t* numel, int L, const double* flat, void* stream) {
-  if (L < 0) return fail(FEDAGG_EINVAL, "promote op: L is negative (L=%lld)", L);
+  if (L < 0) return fail(FEDAGG_EINVAL, "promote op: L is negative (L=%lld)", (long long)L);
   if (L > 0 && !ptrs) return fail(FEDAGG_EINVAL, "promote op: d_layers is NULL");
   if (L > 0 && !numel) return fail(FEDAGG_EINVAL, "promote op: numel is NULL");
   uint64_t total = 0;
@@ -284,11 +275,13 @@ int promote_launch(Kernel kernel, const void* const* ptrs, uint32_t f64, int nli
     for (int j = 0; j < nlists; ++j) {
       const uintptr_t p = reinterpret_cast<uintptr_t>(ptrs[(size_t)j * L + l]);
       const bool is64 = (f64 >> j) & 1u;
-      if (!p && numel[l]) return fail(FEDAGG_EINVAL, "promote op: NULL layer pointer %lld", l);
-      if (is64 && (p & 7u)) return fail(FEDAGG_EINVAL, "promote op: fp64 layer pointer %lld is not 8-B aligned", l);
-      if (!is64 && (p & 1u)) return fail(FEDAGG_EINVAL, "promote op: 16-bit layer pointer %lld is not 2-B aligned", l);
+      if (!p && numel[l]) return fail(FEDAGG_EINVAL, "promote op: NULL layer pointer %lld", (long long)l);
+      if (is64 && (p & 7u))
+        return fail(FEDAGG_EINVAL, "promote op: fp64 layer pointer %lld is not 8-B aligned", (long long)l);
+      if (!is64 && (p & 1u))
+        return fail(FEDAGG_EINVAL, "promote op: 16-bit layer pointer %lld is not 2-B aligned", (long long)l);
     }
-    if (numel[l] > (1ull << 44)) return fail(FEDAGG_EINVAL, "promote op: layer %lld is too large", l);
+    if (numel[l] > (1ull << 44)) return fail(FEDAGG_EINVAL, "promote op: layer %lld is too large", (long long)l);
     total += numel[l];
   }
   if (total && !flat) return fail(FEDAGG_EINVAL, "promote op: the fp64 bucket d_flat is NULL");
@@ -315,7 +308,8 @@ int promote_launch(Kernel kernel, const void* const* ptrs, uint32_t f64, int nli
     }
     a.block_start[nl] = (uint32_t)blocks;
     if (blocks == 0) continue;
-    if (blocks > 0x7fffffffull) return fail(FEDAGG_EINVAL, "promote op: too many elements in one launch group (layer %lld on)", l0);
+    if (blocks > 0x7fffffffull)
+      return fail(FEDAGG_EINVAL, "promote op: too many elements in one launch group (layer %lld on)", (long long)l0);
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(PR_BLOCK), 0, (hipStream_t)stream, a,
                        const_cast<double*>(flat));
     const int rc = check_launch("promote op kernel");
@@ -329,11 +323,11 @@ int promote_launch(Kernel kernel, const void* const* ptrs, uint32_t f64, int nli
 extern "C" {
 
 int fedagg_promote_abi_version(void) { return FEDAGG_PROMOTE_ABI_VERSION; }
-const char* fedagg_promote_last_error(void) { return g_error; }
+const char* fedagg_promote_last_error(void) { return fedagg_lib_error::g_error; }
 
 int fedagg_promote_tune(const char* key, int value) {
   if (!key || strcmp(key, "vec") != 0) return fail(FEDAGG_EINVAL, "promote tune: unknown key");
-  if (value != 0 && value != 1) return fail(FEDAGG_EINVAL, "promote tune: vec takes 0 or 1 (got %lld)", value);
+  if (value != 0 && value != 1) return fail(FEDAGG_EINVAL, "promote tune: vec takes 0 or 1 (got %lld)", (long long)value);
   g_vec.store(value, std::memory_order_relaxed);
   return FEDAGG_OK;
 }
@@ -341,7 +335,7 @@ int fedagg_promote_tune(const char* key, int value) {
 int fedagg_promote_wsum(const void* const* d_layers, const int* kinds, int nlists, const double* coeffs,
                         const uint64_t* numel, int L, double* d_flat, void* stream) {
   if (nlists < 1 || nlists > FEDAGG_FLAT_MAX_LISTS)
-    return fail(FEDAGG_EINVAL, "promote wsum: nlists outside 1..FEDAGG_FLAT_MAX_LISTS (nlists=%lld)", nlists);
+    return fail(FEDAGG_EINVAL, "promote wsum: nlists outside 1..FEDAGG_FLAT_MAX_LISTS (nlists=%lld)", (long long)nlists);
   if (!kinds) return fail(FEDAGG_EINVAL, "promote wsum: kinds is NULL");
   int kind16 = -1;
   uint32_t f64 = 0;
@@ -350,11 +344,12 @@ int fedagg_promote_wsum(const void* const* d_layers, const int* kinds, int nlist
     if (k == FEDAGG_F64) {
       f64 |= 1u << j;
     } else if (k == FEDAGG_F32) {
-      return fail(FEDAGG_EINVAL, "promote wsum: list %lld is fp32 (fedagg_flat_wsum serves fp32 next to fp64)", j);
+      return fail(FEDAGG_EINVAL, "promote wsum: list %lld is fp32 (fedagg_flat_wsum serves fp32 next to fp64)",
+                  (long long)j);
     } else if (!is_16bit_kind(k)) {
-      return fail(FEDAGG_EINVAL, "promote wsum: list %lld has an unsupported kind", j);
+      return fail(FEDAGG_EINVAL, "promote wsum: list %lld has an unsupported kind", (long long)j);
     } else if (kind16 >= 0 && k != kind16) {
-      return fail(FEDAGG_EINVAL, "promote wsum: F16 next to BF16 (list %lld)", j);
+      return fail(FEDAGG_EINVAL, "promote wsum: F16 next to BF16 (list %lld)", (long long)j);
     } else {
       kind16 = k;
     }
@@ -368,7 +363,8 @@ int fedagg_promote_wsum(const void* const* d_layers, const int* kinds, int nlist
 int fedagg_promote_increment(void* const* d_layers, int layer_kind, const uint64_t* numel, int L,
                              const double* d_flat, double multiplier, void* stream) {
   if (!is_16bit_kind(layer_kind))
-    return fail(FEDAGG_EINVAL, "promote increment: layer_kind %lld is not FEDAGG_F16 / FEDAGG_BF16", layer_kind);
+    return fail(FEDAGG_EINVAL, "promote increment: layer_kind %lld is not FEDAGG_F16 / FEDAGG_BF16",
+                (long long)layer_kind);
   return promote_launch(
       layer_kind == FEDAGG_F16 ? promote_increment_kernel<FEDAGG_F16> : promote_increment_kernel<FEDAGG_BF16>,
       static_cast<const void* const*>(static_cast<const void*>(d_layers)), 0u, 1, &multiplier, numel, L,

@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "fedagg_mx.h"
+#include "lib_error.h"
 #include "mx_codec.h"
 #include "pairwise_sum.h"
 
@@ -47,20 +48,8 @@ using fedagg_internal::finite_scale;
 using fedagg_internal::pw_leaf;
 using fedagg_internal::QNAN;
 using fedagg_internal::scale_of;
-
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, long long v = 0) {
-  snprintf(g_error, sizeof(g_error), fmt, v);
-  return code;
-}
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return FEDAGG_OK;
-  snprintf(g_error, sizeof(g_error), "%s: %s", what, hipGetErrorString(e));
-  return FEDAGG_EHIP;
-}
+using fedagg_lib_error::fail;
+constexpr auto check_launch = fedagg_lib_error::check_launch<FEDAGG_OK, FEDAGG_EHIP>;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
@@ -347,7 +336,7 @@ void fill_args(MxArgs& a, const uint8_t* const* codes, const uint8_t* const* sca
 extern "C" {
 
 int fedagg_mx_abi_version(void) { return FEDAGG_MX_ABI_VERSION; }
-const char* fedagg_mx_last_error(void) { return g_error; }
+const char* fedagg_mx_last_error(void) { return fedagg_lib_error::g_error; }
 
 int fedagg_mx_blocking(int* tile_elems, int* k_group) {
   if (tile_elems) *tile_elems = MX_TILE;
@@ -357,26 +346,26 @@ int fedagg_mx_blocking(int* tile_elems, int* k_group) {
 
 int fedagg_mx_fedavg_e4m3(const uint8_t* const* d_codes, const uint8_t* const* d_scales, const float* h_w, int K,
                           uint64_t M, const uint64_t* h_idx, int P, float* d_out, void* stream) {
-  if (K <= 0) return fail(FEDAGG_EINVAL, "mx fedavg: K must be positive (K=%lld)", K);
+  if (K <= 0) return fail(FEDAGG_EINVAL, "mx fedavg: K must be positive (K=%lld)", (long long)K);
   if (!d_codes) return fail(FEDAGG_EINVAL, "mx fedavg: d_codes is NULL");
   if (!d_scales) return fail(FEDAGG_EINVAL, "mx fedavg: d_scales is NULL");
   if (!h_w) return fail(FEDAGG_EINVAL, "mx fedavg: h_w is NULL");
-  if (P < 0) return fail(FEDAGG_EINVAL, "mx fedavg: P is negative (P=%lld)", P);
+  if (P < 0) return fail(FEDAGG_EINVAL, "mx fedavg: P is negative (P=%lld)", (long long)P);
   if (P > 0 && !h_idx) return fail(FEDAGG_EINVAL, "mx fedavg: h_idx is NULL with P > 0");
   if (M == 0) return FEDAGG_OK;
   if (M > (1ull << 44)) return fail(FEDAGG_EINVAL, "mx fedavg: M is too large");
   for (int k = 0; k < K; ++k) {
-    if (!d_codes[k]) return fail(FEDAGG_EINVAL, "mx fedavg: code row %lld is NULL", k);
+    if (!d_codes[k]) return fail(FEDAGG_EINVAL, "mx fedavg: code row %lld is NULL", (long long)k);
     if (reinterpret_cast<uintptr_t>(d_codes[k]) & 15u)
-      return fail(FEDAGG_EINVAL, "mx fedavg: code row %lld is not 16-B aligned", k);
-    if (!d_scales[k]) return fail(FEDAGG_EINVAL, "mx fedavg: scale row %lld is NULL", k);
+      return fail(FEDAGG_EINVAL, "mx fedavg: code row %lld is not 16-B aligned", (long long)k);
+    if (!d_scales[k]) return fail(FEDAGG_EINVAL, "mx fedavg: scale row %lld is NULL", (long long)k);
   }
   if (!d_out) return fail(FEDAGG_EINVAL, "mx fedavg: d_out is NULL");
   if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(FEDAGG_EINVAL, "mx fedavg: d_out is not 4-B aligned");
   for (int p = 0; p < P; ++p)
-    if (h_idx[p] >= M) return fail(FEDAGG_EINVAL, "mx fedavg: numel == 1 index %lld is out of range", p);
+    if (h_idx[p] >= M) return fail(FEDAGG_EINVAL, "mx fedavg: numel == 1 index %lld is out of range", (long long)p);
   if (P > 0 && K > FEDAGG_MX_MAX_PAIRWISE_K)
-    return fail(FEDAGG_EINVAL, "mx fedavg: numel == 1 elements are served up to FEDAGG_MX_MAX_PAIRWISE_K clients (K=%lld)", K);
+    return fail(FEDAGG_EINVAL, "mx fedavg: numel == 1 elements are served up to FEDAGG_MX_MAX_PAIRWISE_K clients (K=%lld)", (long long)K);
 
   const uint64_t nvec = (reinterpret_cast<uintptr_t>(d_out) & 15u) ? 0 : M / MX_VEC;
   const unsigned grid = grid_for(M, MX_TILE);
@@ -432,7 +421,7 @@ int fedagg_mx_fedavg_e4m3(const uint8_t* const* d_codes, const uint8_t* const* d
 
 int fedagg_mx_quantize(const void* d_x, int kind, uint64_t M, uint8_t* d_codes, uint8_t* d_scales, void* stream) {
   if (kind != FEDAGG_F32 && kind != FEDAGG_BF16)
-    return fail(FEDAGG_EINVAL, "mx quantize: kind %lld is not FEDAGG_F32 / FEDAGG_BF16", kind);
+    return fail(FEDAGG_EINVAL, "mx quantize: kind %lld is not FEDAGG_F32 / FEDAGG_BF16", (long long)kind);
   if (M == 0) return FEDAGG_OK;
   if (M > (1ull << 44)) return fail(FEDAGG_EINVAL, "mx quantize: M is too large");
   if (!d_x) return fail(FEDAGG_EINVAL, "mx quantize: d_x is NULL");

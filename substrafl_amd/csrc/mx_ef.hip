@@ -33,6 +33,7 @@
 #include <cstdio>
 
 #include "fedagg_mxef.h"
+#include "lib_error.h"
 #include "mx_codec.h"
 
 #define MXEF_THREADS 256                       // threads per workgroup
@@ -45,13 +46,8 @@ namespace {
 using fedagg_internal::e4m3_of;
 using fedagg_internal::finite_scale;
 using fedagg_internal::scale_of;
-
-thread_local char g_error[256] = "";
-
-int fail(int code, const char* fmt, long long v = 0) {
-  snprintf(g_error, sizeof(g_error), fmt, v);
-  return code;
-}
+using fedagg_lib_error::fail;
+constexpr auto check_launch = fedagg_lib_error::check_launch<FEDAGG_OK, FEDAGG_EHIP>;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -226,7 +222,7 @@ bool overlap(const void* p, uint64_t np, const void* q, uint64_t nq) {
 extern "C" {
 
 int fedagg_mxef_abi_version(void) { return FEDAGG_MXEF_ABI_VERSION; }
-const char* fedagg_mxef_last_error(void) { return g_error; }
+const char* fedagg_mxef_last_error(void) { return fedagg_lib_error::g_error; }
 
 int fedagg_mxef_blocking(int* lane_elems, int* tile_elems, uint64_t* second_step_elems) {
   if (lane_elems) *lane_elems = MXEF_LANE;
@@ -238,7 +234,7 @@ int fedagg_mxef_blocking(int* lane_elems, int* tile_elems, uint64_t* second_step
 int fedagg_mxef_quantize(const void* d_x, int kind, uint64_t M, float* d_res, uint8_t* d_codes, uint8_t* d_scales,
                          void* stream) {
   if (kind != FEDAGG_F32 && kind != FEDAGG_BF16)
-    return fail(FEDAGG_EINVAL, "mxef quantize: kind %lld is not FEDAGG_F32 / FEDAGG_BF16", kind);
+    return fail(FEDAGG_EINVAL, "mxef quantize: kind %lld is not FEDAGG_F32 / FEDAGG_BF16", (long long)kind);
   if (M == 0) return FEDAGG_OK;
   if (M > (1ull << 44)) return fail(FEDAGG_EINVAL, "mxef quantize: M is too large");
   const uint64_t esz = kind == FEDAGG_F32 ? 4 : 2;
@@ -267,10 +263,7 @@ int fedagg_mxef_quantize(const void* d_x, int kind, uint64_t M, float* d_res, ui
   else
     hipLaunchKernelGGL(mxef_quantize_kernel<FEDAGG_BF16>, dim3((unsigned)g), dim3(MXEF_THREADS), 0, (hipStream_t)stream,
                        d_x, mv, M, d_res, d_codes, d_scales, scales16);
-  const hipError_t e = hipGetLastError();
-  if (e == hipSuccess) return FEDAGG_OK;
-  snprintf(g_error, sizeof(g_error), "mxef quantize kernel: %s", hipGetErrorString(e));
-  return FEDAGG_EHIP;
+  return check_launch("mxef quantize kernel");
 }
 
 }  // extern "C"

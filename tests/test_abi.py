@@ -5,6 +5,7 @@ import ctypes
 import re
 from pathlib import Path
 
+import abi_header
 import pytest
 
 from substrafl_amd import _native
@@ -15,11 +16,10 @@ HEADER = Path(__file__).resolve().parents[1] / "include" / "fedagg.h"
 def declared_functions(tuning: bool = False):
     """The functions include/fedagg.h declares for the product library (``tuning``: the
     ``#if FEDAGG_TUNING`` block's instead)."""
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    text = abi_header.strip_comments(HEADER)
     blocks = re.findall(r"^#if FEDAGG_TUNING\n(.*?)^#endif", text, flags=re.S | re.M)
     text = "".join(blocks) if tuning else re.sub(r"^#if FEDAGG_TUNING\n.*?^#endif", "", text, flags=re.S | re.M)
-    names = re.findall(r"^\s*(?:const\s+)?[a-z_0-9]+\s*\*?\s*(fedagg_[a-z0-9_]+)\s*\(", text, flags=re.M)
-    return sorted(set(names))
+    return abi_header.functions_in(text, "fedagg_")
 
 
 def test_header_declares_the_abi():
@@ -158,7 +158,7 @@ def test_c_multi_demo_runs_bit_exact(tmp_path):
 
 def _declared_arity():
     """Function name -> number of parameters, from include/fedagg.h (comments stripped)."""
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
+    text = abi_header.strip_comments(HEADER)
     out = {}
     for m in re.finditer(r"(fedagg_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S):
         params = m.group(2).strip()

@@ -3,12 +3,12 @@ ctypes binding covers exactly that, bad arguments come back as -1 with their own
 HIP call, and the C demo compiles against the headers alone (CPU only: no kernel is launched)."""
 
 import ctypes
-import re
 import shutil
 import subprocess
 import sys
 from pathlib import Path
 
+import abi_header
 import pytest
 
 from substrafl_amd import _native, _native_dense
@@ -18,9 +18,7 @@ HEADER = ROOT / "include" / "fedagg_dense.h"
 
 
 def declared_functions():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?[a-z_0-9]+\s*\*?\s*(fedagg_dense_[a-z0-9_]+)\s*\(", text,
-                                 flags=re.M)))
+    return abi_header.declared_functions(HEADER, "fedagg_dense_")
 
 
 def test_library_exports_every_declared_symbol_and_binding_matches():

@@ -5,11 +5,11 @@ the client option refuse what the MXFP8 route does not carry before any device w
 federation never maps the library."""
 
 import ctypes
-import re
 import subprocess
 import sys
 from pathlib import Path
 
+import abi_header
 import numpy as np
 import pytest
 
@@ -21,8 +21,7 @@ F16, F32, F64, BF16 = _native.FEDAGG_F16, _native.FEDAGG_F32, _native.FEDAGG_F64
 
 
 def _header_names():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?[a-z_0-9]+\s*\*?\s*(fedagg_mx_[a-z0-9_]+)\s*\(", text, flags=re.M)))
+    return abi_header.declared_functions(HEADER, "fedagg_mx_")
 
 
 def test_signatures_are_the_header():

@@ -3,11 +3,11 @@ declares and the binding's SIGNATURES are the header's prototypes, every refusal
 FEDAGG_EINVAL with its own text before any HIP call, ``error_feedback`` is refused where the MXFP8
 wire is not, and a class without it never imports the binding."""
 
-import re
 import subprocess
 import sys
 from pathlib import Path
 
+import abi_header
 import pytest
 
 from substrafl_amd import _native, _native_mxef
@@ -19,8 +19,7 @@ F32, BF16 = _native.FEDAGG_F32, _native.FEDAGG_BF16
 
 def test_signatures_are_the_header_and_the_abi_is_pinned():
     text = HEADER.read_text()
-    code = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    names = sorted(set(re.findall(r"^\s*(?:const\s+)?[a-z_0-9]+\s*\*?\s*(fedagg_mxef_[a-z0-9_]+)\s*\(", code, flags=re.M)))
+    names = abi_header.declared_functions(HEADER, "fedagg_mxef_")
     assert names == sorted(_native_mxef.SIGNATURES) == ["fedagg_mxef_abi_version", "fedagg_mxef_blocking",
                                                         "fedagg_mxef_last_error", "fedagg_mxef_quantize"]
     lib = _native_mxef.load()

@@ -1,5 +1,6 @@
 """The installable package (VERDICT r04 "Next 2"): ``pip wheel`` runs the build hook (setup.py ->
-``__graft_entry__.compile_library``), so the wheel carries ``libfedagg.so`` for gfx950; without
+``__graft_entry__.compile_entry`` over ``LIBRARIES``), so the wheel carries ``libfedagg.so`` and
+every other library of that table for gfx950; without
 hipcc the build fails loudly; the reference's own ``Dependency`` machinery accepts the repo and
 ships that wheel (tests/reference_dependency.py, container only).  No GPU: nothing is launched,
 the installed library is only loaded and its ABI version read."""
@@ -45,6 +46,11 @@ def test_wheel_carries_the_library_and_installs(tmp_path):
     assert not whl.name.endswith("none-any.whl")  # a platform wheel: it holds a gfx950 binary
     names = zipfile.ZipFile(whl).namelist()
     assert any(n.endswith("substrafl_amd/libfedagg.so") for n in names)
+    import __graft_entry__
+
+    for lib in __graft_entry__.LIBRARIES:  # every library of the build table, or a binding finds nothing to load
+        assert any(n.endswith("substrafl_amd/" + lib.name) for n in names), lib.name
+    assert len(__graft_entry__.LIBRARIES) >= 5
     assert any(n.endswith("substrafl_amd/algorithms/accelerate.py") for n in names)
     assert not any("tuning" in n or n.endswith(".o") for n in names)
     r = subprocess.run([sys.executable, "-m", "pip", "install", "--no-deps", "--no-index", "--target",

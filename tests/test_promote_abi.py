@@ -4,11 +4,11 @@ FEDAGG_EINVAL with its own text before any HIP call (so none of this needs a GPU
 a 16-bit model next to fp64 operands on a device loads the library."""
 
 import ctypes
-import re
 import subprocess
 import sys
 from pathlib import Path
 
+import abi_header
 import pytest
 
 from substrafl_amd import _native, _native_promote
@@ -19,9 +19,7 @@ F16, F32, F64, BF16 = _native.FEDAGG_F16, _native.FEDAGG_F32, _native.FEDAGG_F64
 
 
 def _header_names():
-    text = re.sub(r"/\*.*?\*/", "", HEADER.read_text(), flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?[a-z_0-9]+\s*\*?\s*(fedagg_promote_[a-z0-9_]+)\s*\(", text,
-                                 flags=re.M)))
+    return abi_header.declared_functions(HEADER, "fedagg_promote_")
 
 
 def test_signatures_are_the_header():
