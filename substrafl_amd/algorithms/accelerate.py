@@ -68,6 +68,9 @@ def _reference_base(algo_cls):
 
 
 def _export(self, tensors, tag="export"):
+    if getattr(self, "_fedagg_mxfp4", False):
+        residual = _mx_residual(self, tensors) if getattr(self, "_fedagg_error_feedback", False) else None
+        return wm.export_mxfp4(tensors, tag=tag, residual=residual)
     if getattr(self, "_fedagg_mxfp8", False):
         residual = _mx_residual(self, tensors) if getattr(self, "_fedagg_error_feedback", False) else None
         return wm.export_mxfp8(tensors, tag=tag, residual=residual)
@@ -309,8 +312,11 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
     ``ValueError``) quantises the update of an fp32 or bf16 model on the device to OCP MXFP8
     (:func:`.weight_manager.export_mxfp8`: 1.03 bytes per parameter in one buffer; the aggregator's
     fp32 average comes back and is applied by the existing paths; no error feedback or residual
-    is carried between rounds unless ``error_feedback=True``).  ``error_feedback`` (only with
-    ``wire="mxfp8"``; a ``TypeError`` otherwise): the client keeps what the quantiser dropped, an fp32
+    is carried between rounds unless ``error_feedback=True``); ``"mxfp4"`` (FedAvg only, refused in
+    the same ways) quantises it to OCP MXFP4 (:func:`.weight_manager.export_mxfp4`: 4-bit ``e2m1``
+    codes, 0.53 bytes per parameter, three arrays in one buffer; ``libfedagg_mx4.so``,
+    include/fedagg_mx4.h, whose one quantiser also carries the residual).  ``error_feedback`` (only with
+    ``wire="mxfp8"`` or ``"mxfp4"``; a ``TypeError`` otherwise): the client keeps what the quantiser dropped, an fp32
     residual of 4 bytes per parameter in ``_fedagg_mx_residual`` (device memory, and the checkpoint
     key ``"fedagg_mx_residual"``), and adds it to the next round's update before quantising, in one
     fused kernel (``libfedagg_mxef.so``, include/fedagg_mxef.h); the wire format does not change.
@@ -321,12 +327,12 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
     ``train`` runs)."""
     base = _reference_base(algo_cls)
     kind = _BASES[base.__name__]
-    if isinstance(wire, str) and wire != "mxfp8":
-        raise ValueError(f"wire must be True, False or 'mxfp8', not {wire!r}")
-    mxfp8 = wire == "mxfp8"
-    if mxfp8 and kind != "fedavg":
-        raise TypeError(f"wire='mxfp8' is an option of TorchFedAvgAlgo, not of {base.__name__}")
-    if error_feedback and not mxfp8:
+    if isinstance(wire, str) and wire not in ("mxfp8", "mxfp4"):
+        raise ValueError(f"wire must be True, False or 'mxfp8' (or 'mxfp4', the 4-bit wire), not {wire!r}")
+    mxfp8, mxfp4 = wire == "mxfp8", wire == "mxfp4"
+    if (mxfp8 or mxfp4) and kind != "fedavg":
+        raise TypeError(f"wire={wire!r} is an option of TorchFedAvgAlgo, not of {base.__name__}")
+    if error_feedback and not (mxfp8 or mxfp4):
         raise TypeError(f"error_feedback is an option of wire='mxfp8' (TorchFedAvgAlgo), not of wire={wire!r} on "
                         f"{base.__name__}")
     if kind != "newton_raphson" and hessian_check is not None:
@@ -339,6 +345,7 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
     ns = {"__doc__": f"{algo_cls.__name__} with its weight moves on MI355X (substrafl_amd.accelerate_algo).",
           "_fedagg_wire": bool(wire),
           "_fedagg_mxfp8": mxfp8,
+          "_fedagg_mxfp4": mxfp4,
           "__init__": _registering_init(algo_cls.__init__),
           "__module__": __name__}  # type() under ABCMeta would otherwise record "abc"
     if kind == "newton_raphson":

@@ -424,6 +424,56 @@ def export_mxfp8(tensors: Sequence[torch.Tensor], tag: str = "export", residual:
     return bucket_views(host, shapes + [(n_scales,)], [E4M3] * len(shapes) + [E8M0])
 
 
+def export_mxfp4(tensors: Sequence[torch.Tensor], tag: str = "export", residual: Optional[torch.Tensor] = None
+                 ) -> List[np.ndarray]:
+    """The MXFP4 form of ``tensors`` (``wire.py``: ``[codes, scales, shapes]``, packed
+    ``wire.E2M1X2`` codes, ``wire.E8M0`` scales and the ``int64`` shape table), quantised on the
+    device by ``fedagg_mx4_quantize`` from the flat fp32 or bf16 bucket.  Codes and scales share one
+    device buffer, so they leave in ONE D2H copy into one host buffer that also holds the shape
+    table, and the three arrays returned are :class:`wire.BucketArray` views of it: they pickle as
+    that one buffer.  Anything but fp32 or bf16 tensors on a ROCm device is refused
+    (``NotImplementedError``), as :func:`export_mxfp8` refuses it.
+
+    ``residual`` (error feedback): a contiguous fp32 tensor of M elements on the bucket's device;
+    the same kernel then encodes ``fl32(x + residual)`` and overwrites ``residual`` with what the
+    encoding dropped, in the same single pass; any other dtype, device, layout or size is a
+    ``ValueError`` before any device work."""
+    from .. import _native_mx4, runtime
+    from ..wire import E2M1X2, E8M0, MX_BLOCK, mxfp4_shape_table
+
+    tensors = list(tensors)
+    kind = _kind(tensors)
+    if kind not in (_native.FEDAGG_F32, _native.FEDAGG_BF16):
+        dts = sorted({str(t.dtype) for t in tensors})
+        raise NotImplementedError(f"wire='mxfp4': the update of an fp32 or bf16 model on a ROCm device is quantised, "
+                                  f"got {dts} on {sorted({str(t.device) for t in tensors})}")
+    M = sum(t.numel() for t in tensors)
+    if residual is not None:
+        if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32 or not residual.is_contiguous():
+            raise ValueError("export_mxfp4: residual must be a contiguous float32 tensor, got "
+                             f"{getattr(residual, 'dtype', type(residual).__name__)}")
+        if residual.device != tensors[0].device:
+            raise ValueError(f"export_mxfp4: residual is on {residual.device}, the bucket on {tensors[0].device}")
+        if residual.numel() != M:
+            raise ValueError(f"export_mxfp4: residual holds {residual.numel()} elements, the bucket {M}")
+    flat = flat_bucket(tensors)
+    if flat is None:
+        flat = _gather_flat(tensors)
+    table = mxfp4_shape_table([tuple(t.shape) for t in tensors])
+    n_codes, n_scales = -(-M // 2), -(-M // MX_BLOCK)
+    dev = torch.empty(n_codes + n_scales, dtype=torch.uint8, device=flat.device)
+    _native_mx4.quantize(flat.data_ptr(), kind, M, residual.data_ptr() if residual is not None else None,
+                         dev.data_ptr(), dev.data_ptr() + n_codes, _stream(flat.device))
+    # one host buffer: the shape table first (8-B aligned), then the codes and the scales as they left the device
+    host = runtime.reusable_host_array(table.nbytes + n_codes + n_scales, np.dtype(np.uint8), tag)
+    host[: table.nbytes] = table.view(np.uint8)
+    torch.cuda.current_stream(flat.device).synchronize()  # the quantiser ran on torch's stream
+    with runtime.device_lock(flat.device.index):  # the session's ring is shared with the engine
+        runtime.session(flat.device.index).fetch(dev.data_ptr(), host[table.nbytes :])
+    t, c, s = bucket_views(host, [(table.size,), (n_codes,), (n_scales,)], [np.dtype(np.int64), E2M1X2, E8M0])
+    return [c, s, t]
+
+
 def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = "export") -> List[np.ndarray]:
     """``[p.cpu().detach().numpy() for p in ...]`` (torch_fed_avg_algo.py:227-230) with ONE D2H copy
     when the tensors are views of one flat bucket.  With ``wire`` the arrays returned are

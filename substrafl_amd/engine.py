@@ -38,7 +38,8 @@ import numpy as np
 
 from . import _native, handoff, runtime
 from .layout import BucketLayout
-from .wire import BF16, E4M3, E8M0, MX_BLOCK, flat_of, has_mxfp8, mxfp8_check
+from .wire import (BF16, E2M1X2, E4M3, E8M0, MX_BLOCK, flat_of, has_mxfp4, has_mxfp8, mxfp4_check, mxfp4_layer_shapes,
+                   mxfp8_check)
 
 KINDS = ("f32", "bf16", "f64", "f16")
 BF16_GROUP = "bf16"  # fedavg()'s dtype-group key of wire.BF16 layers (the others are NumPy dtype strings)
@@ -93,7 +94,13 @@ def reject_bf16(rows, what: str) -> None:
 def reject_mxfp8(rows, what: str) -> None:
     """MXFP8 updates (``wire.E4M3`` codes, ``wire.E8M0`` scales) hold bit patterns: only FedAvg on
     the single-GPU in-core route (:meth:`AggregationEngine.fedavg_mxfp8`) decodes them, every
-    other route refuses them by name."""
+    other route refuses them by name; so it is with MXFP4 updates (``wire.E2M1X2`` codes) and
+    :meth:`AggregationEngine.fedavg_mxfp4`."""
+    for row in rows:
+        for a in row:
+            if getattr(a, "dtype", None) == E2M1X2:  # first: an MXFP4 update carries wire.E8M0 too
+                raise NotImplementedError(f"{what}: no MXFP4 path for wire.E2M1X2 arrays "
+                                          "(FedAvg on one GPU, in core, aggregates them)")
     for row in rows:
         for a in row:
             if getattr(a, "dtype", None) in (E4M3, E8M0):
@@ -491,6 +498,19 @@ def c_mismatches16(c_rows) -> Tuple[int, str]:
             va, vb = (bf16_to_float32(a), bf16_to_float32(b)) if a.dtype == BF16 else (a, b)
             mism += int(np.count_nonzero(~((va == vb) | (np.isnan(va) & np.isnan(vb)))))
     return mism, path
+
+
+def mxfp4_first(method):
+    """``AggregationEngine.fedavg`` with updates that carry ``wire.E2M1X2`` sent to
+    :meth:`AggregationEngine.fedavg_mxfp4`, whose refusals come before any lock or device work."""
+
+    @functools.wraps(method)
+    def wrapper(self, parameters_updates, n_samples, wire=False):
+        if parameters_updates and any(has_mxfp4(pu) for pu in parameters_updates):
+            return self.fedavg_mxfp4(parameters_updates, n_samples, wire)
+        return method(self, parameters_updates, n_samples, wire)
+
+    return wrapper
 
 
 def serialized(method):
@@ -929,6 +949,8 @@ class AggregationEngine:
         whose buckets exceed the budget are streamed through the GPU in parameter ranges
         (``MultiDeviceEngine.fedavg_routed`` with this one device) where :meth:`fedavg` refuses
         them; that refusal is pinned by tests, so the route is this name."""
+        if parameters_updates and any(has_mxfp4(pu) for pu in parameters_updates):
+            return self.fedavg_mxfp4(parameters_updates, n_samples, wire)  # ahead of MXFP8: both carry wire.E8M0
         if parameters_updates and any(has_mxfp8(pu) for pu in parameters_updates):
             return self.fedavg_mxfp8(parameters_updates, n_samples, wire)  # the MXFP8 wire (DESIGN §2)
         if (parameters_updates and parameters_updates[0]
@@ -948,6 +970,88 @@ class AggregationEngine:
         out = ooc.fedavg_routed(parameters_updates, n_samples, wire)
         self.last_timing = {"out_of_core": ooc.last_timing, "staging": "out-of-core"}
         return out
+
+    # ----------------------------------------------------------------------------------
+    def fedavg_mxfp4(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
+                     wire: bool = False) -> List[np.ndarray]:
+        """FedAvg over MXFP4 updates (``[codes, scales, shapes]`` per client: ``wire.E2M1X2`` packed
+        codes, ``wire.E8M0`` scales and the ``int64`` shape table): bit-identical to fed_avg.py:217-222
+        on the exactly decoded fp32 inputs (``wire.mxfp4_to_float32``).  The K code rows and the K
+        scale rows are staged as two byte buckets, ``fedagg_mx4_fedavg_e2m1`` reduces them in one
+        call and the L fp32 layers come home (``wire``: as :class:`wire.BucketArray` layers of one
+        bucket).
+
+        Refused before any device work: clients of which only some are MXFP4
+        (``NotImplementedError``), an update that is not the three arrays or whose code or scale
+        array has the wrong length, shape tables that differ between clients (``ValueError``),
+        numel == 1 layers over more clients than the library's pairwise patch serves, the device
+        hand-off and buckets beyond the in-core budget (``NotImplementedError``, each naming its
+        route)."""
+        from . import _native_mx4
+
+        K = len(parameters_updates)
+        n_mx = sum(1 for pu in parameters_updates if has_mxfp4(pu))
+        if n_mx != K:
+            raise NotImplementedError(f"FedAvg engine: {n_mx} of {K} clients sent MXFP4 updates; the MXFP4 route "
+                                      "takes MXFP4 from every client or from none")
+        Ms = [mxfp4_check(pu) for pu in parameters_updates]
+        shapes = mxfp4_layer_shapes(parameters_updates[0][2])
+        for pu in parameters_updates[1:]:
+            if not np.array_equal(np.asarray(pu[2]), np.asarray(parameters_updates[0][2])):
+                raise ValueError("FedAvg engine: MXFP4 shape tables differ between clients")
+        M = Ms[0]
+        layout = BucketLayout(range(len(shapes)), shapes, np.float32)  # the fp32 result; its numel == 1 indices
+        if layout.pairwise_idx.size and K > _native_mx4.MAX_PAIRWISE_K:
+            raise NotImplementedError(f"FedAvg engine: the MXFP4 route serves numel == 1 layers up to "
+                                      f"{_native_mx4.MAX_PAIRWISE_K} clients (got {K})")
+        if handoff.enabled():
+            raise NotImplementedError("FedAvg engine: the device hand-off has no MXFP4 route")
+        return self._fedavg_mxfp4(parameters_updates, n_samples, wire, layout, M)
+
+    @serialized
+    def _fedavg_mxfp4(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, M: int):
+        from . import _native_mx4
+
+        t_start = time.perf_counter()
+        K = len(parameters_updates)
+        ld_c = -(-(-(-M // 2)) // 256) * 256  # code bytes per row: 16-B aligned rows
+        ld_s = -(-(-(-M // MX_BLOCK)) // 256) * 256
+        need = K * (ld_c + ld_s) + 4 * layout.ld
+        slots = (self._B_BUCKET, self._B_CV, self._B_OUT)
+        if self.max_bucket_bytes is not None:
+            budget = int(self.max_bucket_bytes)
+        else:
+            from .multi_device import HBM_HEADROOM
+
+            budget = int((runtime.device_memory(self._index())[0] + self.session().held_bytes(slots)) * HBM_HEADROOM)
+        if need > budget:
+            raise NotImplementedError(f"FedAvg engine: the out-of-core route has no MXFP4 path ({need} bytes do "
+                                      "not fit the bucket budget)")
+        s = self.session()
+        self.last_timing = tm = {}
+        self._prestaged = {}
+        row = lambda a: [np.ascontiguousarray(a).reshape(-1).view(np.uint8)]  # noqa: E731  (one segment per client)
+
+        t0 = time.perf_counter()
+        d_codes = s.buffer(self._B_BUCKET, K * ld_c)
+        s.stage(d_codes, ld_c, [row(pu[0]) for pu in parameters_updates])
+        d_scales = s.buffer(self._B_CV, K * ld_s)
+        s.stage(d_scales, ld_s, [row(pu[1]) for pu in parameters_updates])
+        tm["staging"] = "mxfp4-host-rows"
+        tm["prestaged"] = False
+        tm["layout"] = "rows"
+        tm["stage_s"] = time.perf_counter() - t0
+        d_out = s.buffer(self._B_OUT, layout.ld * 4)
+        t1 = time.perf_counter()
+        _native_mx4.fedavg_e2m1([d_codes + k * ld_c for k in range(K)], [d_scales + k * ld_s for k in range(K)],
+                                fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx, d_out, s.stream)
+        out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp4")
+        s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+        tm.update({f"native_{k}": v for k, v in s.timing().items()})
+        tm["total_s"] = time.perf_counter() - t_start
+        return [results[li] for li in range(len(results))]
 
     # ----------------------------------------------------------------------------------
     def fedavg_mxfp8(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
@@ -1037,6 +1141,7 @@ class AggregationEngine:
         return results  # type: ignore[return-value]
 
     # ----------------------------------------------------------------------------------
+    @mxfp4_first
     @serialized
     def fedavg(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
                wire: bool = False) -> List[np.ndarray]:

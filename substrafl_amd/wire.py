@@ -199,6 +199,200 @@ def mxfp8_to_float32(codes, scales):
     return out if many else out[0]
 
 
+# ------------------------------------------------------------------------------------------
+# OCP MXFP4: 4-bit ``e2m1`` elements, two to a byte, one ``e8m0`` scale per block of 32
+# (include/fedagg_mx4.h states the same rules).
+#
+# Layers cannot be views of packed nibbles, so a quantised update is three arrays,
+# ``[codes, scales, shapes]``: ``codes`` a 1-D :data:`E2M1X2` array of ``ceil(M / 2)`` bytes over
+# the raveled concatenation of the layers, ``scales`` the 1-D :data:`E8M0` array of
+# ``ceil(M / 32)`` bytes, ``shapes`` a 1-D ``int64`` array holding L, then per layer ``ndim`` and
+# the dims.
+#
+# Element.  ``e2m1`` has 1 sign bit (bit 3), 2 exponent bits and 1 mantissa bit: the magnitudes of
+# the codes 0..7 are 0, 0.5, 1, 1.5, 2, 3, 4, 6; there is no NaN and no infinity.  Packing.  Flat
+# element 2j is in bits 3:0 of byte j, element 2j+1 in bits 7:4; the unused high nibble of an odd M
+# is written as 0 and never read.  Blocks.  Block b covers flat elements
+# ``[32 b, min(32 b + 32, M))``: 16 code bytes and one scale byte s.
+#
+# Decode.  ``x = fl32(v 2^(s - 127))``; s == 255 makes the whole block NaN.  Every finite product
+# is an fp32 value (the smallest granule is 2^-128, a subnormal; nothing is flushed); the one
+# inexact case is overflow to +-inf (|v| >= 2 under s = 254, |v| >= 4 under s = 253).
+#
+# Encode, per block, amax = max |x_i|: any NaN or Inf: s = 255 and every code 0.  amax == 0:
+# s = 127 and the codes carry the zeros' signs.  Else e = floor(log2(amax)) - 2, e += 1 if
+# amax 2^-e >= 7 (7 is the tie that rounds to the missing 8, so after the bump nothing saturates),
+# e clamped to [-127, 127], s = e + 127; an element is y = fl32(x 2^-e) rounded to nearest even
+# among the e2m1 values, |y| >= 6 to +-6, the sign of zero kept.
+#
+# Error feedback (:func:`mxfp4_error_feedback`): r = fl32(x + res), encode r, res' = fl32(r - d)
+# where the block is finite and the decode d is finite, +0.0 otherwise (include/fedagg_mxef.h).
+E2M1X2 = np.dtype([("e2m1x2", "u1")])
+E2M1_VALUES = np.array([0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0])
+
+
+def has_mxfp4(parameters_update) -> bool:
+    """Whether any array of ``parameters_update`` carries :data:`E2M1X2`."""
+    return any(getattr(a, "dtype", None) == E2M1X2 for a in parameters_update)
+
+
+def is_mxfp4(parameters_update) -> bool:
+    """Whether ``parameters_update`` has the MXFP4 form ``[codes, scales, shapes]`` by its dtypes
+    (the lengths are checked by :func:`mxfp4_check`)."""
+    pu = list(parameters_update) if isinstance(parameters_update, (list, tuple)) else []
+    return len(pu) == 3 and [getattr(a, "dtype", None) for a in pu] == [E2M1X2, E8M0, np.dtype(np.int64)]
+
+
+def mxfp4_shape_table(shapes) -> np.ndarray:
+    """The ``int64`` shape table of the layers ``shapes``: L, then per layer ``ndim`` and the dims."""
+    t = [len(shapes)]
+    for s in shapes:
+        t += [len(s), *[int(d) for d in s]]
+    return np.array(t, dtype=np.int64)
+
+
+def mxfp4_layer_shapes(table) -> List[Tuple[int, ...]]:
+    """The layer shapes a shape table holds; ``ValueError`` when it is not one."""
+    t = np.asarray(table)
+    bad = ValueError("MXFP4 update: the shape table is not a 1-D int64 array of L, then per layer ndim and the dims")
+    if t.dtype != np.int64 or t.ndim != 1 or t.size < 1 or t[0] < 0:
+        raise bad
+    out, p = [], 1
+    for _ in range(int(t[0])):
+        if p >= t.size or t[p] < 0 or p + 1 + int(t[p]) > t.size:
+            raise bad
+        nd = int(t[p])
+        if (t[p + 1 : p + 1 + nd] < 0).any():
+            raise bad
+        out.append(tuple(int(d) for d in t[p + 1 : p + 1 + nd]))
+        p += 1 + nd
+    if p != t.size:
+        raise bad
+    return out
+
+
+def mxfp4_check(parameters_update) -> int:
+    """M of an MXFP4 update ``[codes, scales, shapes]``; ``ValueError`` when it is not three arrays
+    of :data:`E2M1X2`, :data:`E8M0` and ``int64``, or the code array does not hold ``ceil(M / 2)``
+    bytes or the scale array ``ceil(M / 32)`` for the M of the shape table."""
+    pu = list(parameters_update)
+    if not is_mxfp4(pu):
+        raise ValueError("MXFP4 update: expected [codes (wire.E2M1X2), scales (wire.E8M0), shapes (int64)], got "
+                         f"{[str(getattr(a, 'dtype', type(a).__name__)) for a in pu]}")
+    M = sum(int(np.prod(s, dtype=np.int64)) for s in mxfp4_layer_shapes(pu[2]))
+    c, s = np.asarray(pu[0]), np.asarray(pu[1])
+    if c.ndim != 1 or c.size != -(-M // 2):
+        raise ValueError(f"MXFP4 update: {M} elements need a 1-D code array of {-(-M // 2)} bytes, got shape {c.shape}")
+    if s.ndim != 1 or s.size != -(-M // MX_BLOCK):
+        raise ValueError(f"MXFP4 update: {M} elements need a 1-D scale array of {-(-M // MX_BLOCK)} bytes, "
+                         f"got shape {s.shape}")
+    return M
+
+
+def _e2m1_round(y: np.ndarray) -> np.ndarray:
+    """fp32 ``y`` (finite) to 4-bit e2m1 codes: nearest even, |y| >= 6 to +-6, signed zeros."""
+    u = np.ascontiguousarray(y, np.float32).view(np.uint32)
+    a = u & np.uint32(0x7FFFFFFF)
+    # below 1 the e2m1 values are the multiples of 0.5: |y| + 2^22 rounds there (fp32 ulp 0.5)
+    with np.errstate(all="ignore"):
+        sub = (np.minimum(a, np.uint32(0x3F800000)).view(np.float32) + np.float32(4194304.0)).view(np.uint32) \
+            - np.uint32(0x4A800000)
+    a_n = np.clip(a, np.uint32(0x3F800000), np.uint32(0x40C00000))  # [1, 6]: keeps the shifts below in range
+    nrm = (a_n + np.uint32(0x1FFFFF) + ((a_n >> np.uint32(22)) & np.uint32(1)) - np.uint32(0x3F000000)) >> np.uint32(22)
+    code = np.where(a < np.uint32(0x3F800000), sub, nrm)
+    code = np.where(a >= np.uint32(0x40C00000), np.uint32(7), code)
+    return (code | ((u >> np.uint32(28)) & np.uint32(8))).astype(np.uint8)
+
+
+def _mx4_encode_flat(x: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(the M 4-bit codes, one per byte; the scale bytes) of the flat fp32 ``x``."""
+    M = x.size
+    nb = -(-M // MX_BLOCK)
+    pad = np.zeros(nb * MX_BLOCK, np.float32)
+    pad[:M] = x
+    pad = pad.reshape(nb, MX_BLOCK)
+    a = (pad.view(np.uint32) & np.uint32(0x7FFFFFFF)).max(axis=1) if nb else np.zeros(0, np.uint32)
+    bad = a >= np.uint32(0x7F800000)
+    zero = a == 0
+    amax = a.view(np.float32).astype(np.float64)
+    amax[bad | zero] = 1.0
+    e = np.frexp(amax)[1].astype(np.int64) - 3  # floor(log2(amax)) - 2
+    e += np.ldexp(amax, -e) >= 7.0
+    e = np.clip(e, -127, 127)
+    e[bad | zero] = 0
+    s = (e + 127).astype(np.uint8)
+    s[bad] = 255
+    inv = np.ldexp(1.0, -e).astype(np.float32)  # 2^-e, exact (2^-127 is an fp32 subnormal)
+    with np.errstate(all="ignore"):
+        y = pad * inv[:, None]
+    codes = _e2m1_round(y)
+    codes[bad, :] = 0
+    return codes.reshape(-1)[:M].copy(), s
+
+
+def _mx4_pack(codes: np.ndarray) -> np.ndarray:
+    c = np.zeros(-(-codes.size // 2) * 2, np.uint8)
+    c[: codes.size] = codes
+    return c[0::2] | (c[1::2] << np.uint8(4))
+
+
+def _mx4_decode_flat(packed: np.ndarray, s: np.ndarray, M: int) -> np.ndarray:
+    c = np.stack([packed & 15, packed >> 4], axis=1).reshape(-1)[:M]
+    sc = np.ldexp(1.0, s.astype(np.int64) - 127)
+    sc[s == 255] = np.nan
+    with np.errstate(all="ignore"):
+        return np.copysign(E2M1_VALUES[c & 7] * np.repeat(sc, MX_BLOCK)[:M],
+                           np.where(c & 8, -1.0, 1.0)).astype(np.float32)
+
+
+def float32_to_mxfp4(x):
+    """``x`` (an array, or a list of layers; cast to fp32) encoded by the rule above:
+    ``(codes, scales, shapes)``, the three arrays of an MXFP4 update."""
+    arrs = [np.asarray(a, dtype=np.float32) for a in (x if isinstance(x, (list, tuple)) else [x])]
+    flat = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.float32)
+    codes, s = _mx4_encode_flat(flat)
+    return _mx4_pack(codes).view(E2M1X2), s.view(E8M0), mxfp4_shape_table([a.shape for a in arrs])
+
+
+def mxfp4_to_float32(codes, scales, shapes=None):
+    """The exact fp32 values of the MXFP4 ``codes`` (:data:`E2M1X2`) under ``scales``
+    (:data:`E8M0`): a list of layers shaped by the shape table ``shapes``, or, with ``shapes`` an int
+    M or None (then ``2 len(codes)``), the flat array of M elements."""
+    codes, scales = np.asarray(codes), np.asarray(scales)
+    if codes.dtype != E2M1X2 or scales.dtype != E8M0:
+        raise TypeError("mxfp4_to_float32: expected wire.E2M1X2 codes and wire.E8M0 scales")
+    layers = None if shapes is None or np.ndim(shapes) == 0 else mxfp4_layer_shapes(shapes)
+    c, s = codes["e2m1x2"].reshape(-1), scales["e8m0"].reshape(-1)
+    if layers is not None:
+        M = sum(int(np.prod(sh, dtype=np.int64)) for sh in layers)
+    else:
+        M = 2 * c.size if shapes is None else int(shapes)
+    if c.size != -(-M // 2) or s.size != -(-M // MX_BLOCK):
+        raise ValueError(f"mxfp4_to_float32: {M} elements need {-(-M // 2)} code bytes and {-(-M // MX_BLOCK)} scale "
+                         f"bytes, got {c.size} and {s.size}")
+    v = _mx4_decode_flat(c, s, M)
+    if layers is None:
+        return v
+    out, off = [], 0
+    for sh in layers:
+        n = int(np.prod(sh, dtype=np.int64))
+        out.append(v[off : off + n].reshape(sh))
+        off += n
+    return out
+
+
+def mxfp4_error_feedback(x, res):
+    """One error-feedback step on the flat fp32 ``x`` and residual ``res``:
+    ``(codes, scales, res')`` with ``codes`` and ``scales`` as :func:`float32_to_mxfp4` gives them
+    for ``r = fl32(x + res)``."""
+    with np.errstate(all="ignore"):
+        r = np.asarray(x, np.float32).reshape(-1) + np.asarray(res, np.float32).reshape(-1)
+        codes, scales, _ = float32_to_mxfp4(r)
+        d = mxfp4_to_float32(codes, scales, r.size)
+        keep = np.isfinite(d) & np.repeat(scales["e8m0"] != 255, MX_BLOCK)[: r.size]
+        return codes, scales, np.where(keep, r - d, np.float32(0.0)).astype(np.float32)
+
+
 class _Bucket:
     """Owner of one flat byte buffer (1-D uint8, C-contiguous, writable)."""
 
