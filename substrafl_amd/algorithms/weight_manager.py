@@ -40,7 +40,7 @@ import torch
 from torch._utils import _unflatten_dense_tensors
 
 from .. import _native, _native_promote
-from ..wire import BF16, bucket_views, flat_of
+from ..wire import BF16, bucket_views, flat_of, has_mxfp8
 
 _BN = (
     torch.nn.BatchNorm1d,
@@ -180,6 +180,8 @@ def increment_parameters(
     """``w += updates_multiplier * u`` for every model parameter (weight_manager.py:103-137)."""
     with torch.no_grad():
         params = list(model_parameters(model=model, with_batch_norm_parameters=with_batch_norm_parameters)())
+        if has_mxfp8(updates):  # the MXFP8 downlink: L code layers and the scale array, so one array more
+            return _increment_mxfp8(params, list(updates), updates_multiplier)
         assert len(params) == len(updates), "Length of model parameters and updates are unequal."
         for w, u in zip(params, updates):
             assert tuple(u.shape) == tuple(w.data.shape), (
@@ -218,6 +220,73 @@ def increment_parameters(
                 u = (torch.from_numpy(u.view(np.int16)).view(torch.bfloat16) if u.dtype == BF16
                      else torch.from_numpy(u)).to(w.device)
             w.data += updates_multiplier * u.data
+
+
+def _increment_mxfp8(params, updates, multiplier: float) -> None:
+    """``w += multiplier * decode(update)`` for an MXFP8 ``update`` (``wire.py``: L ``wire.E4M3``
+    layers, then the ``wire.E8M0`` scale array; what ``FedAvg(downlink="mxfp8")`` sends back).  Codes
+    and scales are staged to the model's device as ONE byte bucket, 1.03 bytes per parameter; an fp32
+    model then takes ``fedagg_mxdl_increment`` (decode and add in one pass over the parameter
+    tensors, the bits of ``fedagg_flat_increment`` on the decoded layers), a bf16 model
+    ``fedagg_mxdl_decode`` into an fp32 bucket and the existing fp32-onto-bf16 increment.
+
+    ``ValueError``: not the MXFP8 form, a layer count or shape that differs from the parameters, a
+    scale array of the wrong length.  ``NotImplementedError``, naming the downlink: parameters on
+    the CPU, or of any dtype but fp32 or bf16 -- there is no host decoder behind this."""
+    from .. import _native_mxdl
+    from ..wire import is_mxfp8, mxfp8_check
+
+    if not is_mxfp8(updates):
+        raise ValueError("MXFP8 update: expected wire.E4M3 layers, then one trailing wire.E8M0 scale array, got "
+                         f"{[str(getattr(u, 'dtype', type(u).__name__)) for u in updates]}")
+    M = mxfp8_check(updates)  # the scale count against M
+    layers, scales = updates[:-1], updates[-1]
+    if len(layers) != len(params):
+        raise ValueError(f"MXFP8 update: {len(layers)} layers for {len(params)} model parameters")
+    for w, u in zip(params, layers):
+        if tuple(u.shape) != tuple(w.data.shape):
+            raise ValueError(f"MXFP8 update: the shape of the model weights ({tuple(w.data.shape)}) and of the update "
+                             f"({tuple(u.shape)}) are unequal")
+    pkind = _kind([p.data for p in params])
+    if pkind not in (_native.FEDAGG_F32, _native.FEDAGG_BF16):
+        strided = [i for i, p in enumerate(params) if not p.data.is_contiguous()]
+        raise NotImplementedError(
+            "downlink='mxfp8': the MXFP8 average is decoded onto contiguous parameters of one dtype, fp32 or bf16, "
+            f"on one ROCm device; got {sorted({str(p.dtype) for p in params})} on "
+            f"{sorted({str(p.device) for p in params})}" + (f", parameters {strided} not contiguous" if strided else ""))
+    if M == 0:
+        return
+    device = params[0].device
+    bucket = _stage_host_bytes([*layers, scales], device)  # codes, then ceil(M / 32) scale bytes
+    d_codes, d_scales, stream = bucket.data_ptr(), bucket.data_ptr() + M, _stream(device)
+    ptrs, numels = [p.data.data_ptr() for p in params], [p.numel() for p in params]
+    if pkind == _native.FEDAGG_F32:
+        _native_mxdl.increment(ptrs, numels, d_codes, d_scales, M, float(multiplier), stream)
+        return
+    flat = torch.empty(M, dtype=torch.float32, device=device)
+    _native_mxdl.decode(d_codes, d_scales, M, flat.data_ptr(), stream)
+    lib = _native.load()
+    _native.check(lib.fedagg_flat_increment_kind(_native.ptr_array(ptrs), pkind, _numel_array(params), len(params),
+                                                 flat.data_ptr(), _native.FEDAGG_F32, float(multiplier), stream),
+                  "flat_increment_kind")
+
+
+def _stage_host_bytes(arrays: Sequence[np.ndarray], device) -> torch.Tensor:
+    """Host arrays of any dtypes -> ONE flat ``uint8`` device bucket holding their bytes back to back,
+    through the native session's pinned ring like :func:`_stage_host_layers` (one row of segments)."""
+    from .. import runtime
+
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    segs = [np.ascontiguousarray(a).reshape(-1).view(np.uint8) for a in arrays]
+    flat = torch.empty(sum(int(a.size) for a in segs), dtype=torch.uint8, device=torch.device("cuda", idx))
+    if flat.numel():
+        # the bucket may reuse memory torch's stream still reads: the copy starts after that stream
+        torch.cuda.current_stream(flat.device).synchronize()
+        with runtime.device_lock(idx):  # the session's ring is shared with the aggregation engine
+            s = runtime.session(idx)
+            s.stage(flat.data_ptr(), flat.numel(), [segs])
+            s.sync()
+    return flat
 
 
 def _device_flat(updates, device) -> Optional[torch.Tensor]:

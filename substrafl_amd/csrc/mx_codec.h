@@ -1,6 +1,6 @@
 // mx_codec.h -- the MXFP8 element codec as device code (the rules of include/fedagg_mx.h), shared
-// by mx.hip (libfedagg_mx.so) and mx_ef.hip (libfedagg_mxef.so).  Every helper carries
-// `#pragma clang fp contract(off)`; both files are compiled with -ffp-contract=off.
+// by mx.hip (libfedagg_mx.so), mx_ef.hip (libfedagg_mxef.so) and mx_down.hip (libfedagg_mxdl.so).
+// Every helper carries `#pragma clang fp contract(off)`; the files are compiled with -ffp-contract=off.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -64,6 +64,33 @@ __device__ __forceinline__ uint32_t finite_scale(const uint32_t a, float& inv) {
   const uint32_t f = (uint32_t)(127 - e);                      // exponent field of 2^-e
   inv = __uint_as_float(f ? f << 23 : 0x00400000u);            // 2^-127 is a subnormal
   return (uint32_t)(e + 127);
+}
+
+// What a block's maximum decides: the scale byte, 2^-e for the encode and 2^(s-127) for the decode.
+struct BlockScale {
+  uint32_t s;
+  float inv, f;
+  bool bad, zero;  // NaN or Inf in the block; every element +-0
+};
+
+__device__ __forceinline__ BlockScale block_scale(const uint32_t a) {
+  BlockScale b;
+  b.bad = a >= 0x7F800000u;
+  b.zero = a == 0u;
+  const uint32_t s = finite_scale((b.bad || b.zero) ? 0x3F800000u : a, b.inv);
+  b.s = b.bad ? 255u : (b.zero ? 127u : s);
+  b.f = scale_of(b.zero ? 127u : s);  // finite also for a bad block: its res' is selected below
+  return b;
+}
+
+// The code of r under the block's scale (a bad block's codes are 0x00; a zero block's carry the signs:
+// +-0 * inv is +-0 and e4m3_of(0) is 0).
+__device__ __forceinline__ uint32_t encode(const float r, const BlockScale& b) {
+#pragma clang fp contract(off)
+  const float y = r * b.inv;
+  const uint32_t yu = __float_as_uint(y);
+  const uint32_t c = e4m3_of(yu & 0x7FFFFFFFu) | ((yu >> 24) & 0x80u);
+  return b.bad ? 0u : c;
 }
 
 }  // namespace fedagg_internal

@@ -43,9 +43,9 @@
 
 namespace {
 
-using fedagg_internal::e4m3_of;
-using fedagg_internal::finite_scale;
-using fedagg_internal::scale_of;
+using fedagg_internal::block_scale;
+using fedagg_internal::BlockScale;
+using fedagg_internal::encode;
 using fedagg_lib_error::fail;
 constexpr auto check_launch = fedagg_lib_error::check_launch<FEDAGG_OK, FEDAGG_EHIP>;
 
@@ -59,33 +59,6 @@ __device__ __forceinline__ uint32_t quad_max(uint32_t a) {
   a = o > a ? o : a;
   o = (uint32_t)__builtin_amdgcn_mov_dpp((int)a, 0x4E, 0xF, 0xF, true);
   return o > a ? o : a;
-}
-
-// What a block's maximum decides: the scale byte, 2^-e for the encode and 2^(s-127) for the decode.
-struct BlockScale {
-  uint32_t s;
-  float inv, f;
-  bool bad, zero;  // NaN or Inf in the block; every element +-0
-};
-
-__device__ __forceinline__ BlockScale block_scale(const uint32_t a) {
-  BlockScale b;
-  b.bad = a >= 0x7F800000u;
-  b.zero = a == 0u;
-  const uint32_t s = finite_scale((b.bad || b.zero) ? 0x3F800000u : a, b.inv);
-  b.s = b.bad ? 255u : (b.zero ? 127u : s);
-  b.f = scale_of(b.zero ? 127u : s);  // finite also for a bad block: its res' is selected below
-  return b;
-}
-
-// The code of r under the block's scale (a bad block's codes are 0x00; a zero block's carry the signs:
-// +-0 * inv is +-0 and e4m3_of(0) is 0).
-__device__ __forceinline__ uint32_t encode(const float r, const BlockScale& b) {
-#pragma clang fp contract(off)
-  const float y = r * b.inv;
-  const uint32_t yu = __float_as_uint(y);
-  const uint32_t c = e4m3_of(yu & 0x7FFFFFFFu) | ((yu >> 24) & 0x80u);
-  return b.bad ? 0u : c;
 }
 
 // res' from r and the hardware's decode v of its code.

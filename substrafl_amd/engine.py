@@ -38,8 +38,8 @@ import numpy as np
 
 from . import _native, handoff, runtime
 from .layout import BucketLayout
-from .wire import (BF16, E2M1X2, E4M3, E8M0, MX_BLOCK, flat_of, has_mxfp4, has_mxfp8, mxfp4_check, mxfp4_layer_shapes,
-                   mxfp8_check)
+from .wire import (BF16, E2M1X2, E4M3, E8M0, MX_BLOCK, bucket_views, flat_of, has_mxfp4, has_mxfp8, mxfp4_check,
+                   mxfp4_layer_shapes, mxfp8_check)
 
 KINDS = ("f32", "bf16", "f64", "f16")
 BF16_GROUP = "bf16"  # fedavg()'s dtype-group key of wire.BF16 layers (the others are NumPy dtype strings)
@@ -106,6 +106,20 @@ def reject_mxfp8(rows, what: str) -> None:
             if getattr(a, "dtype", None) in (E4M3, E8M0):
                 raise NotImplementedError(f"{what}: no MXFP8 path for wire.E4M3 / wire.E8M0 arrays "
                                           "(FedAvg on one GPU, in core, aggregates them)")
+
+
+def mx_downlink_bytes(M: int) -> Tuple[int, int]:
+    """(offset of the scale bytes, size) of the buffer that holds an MXFP8-encoded average of M
+    elements: M code bytes, then ``ceil(M / 32)`` scale bytes from the next multiple of 16."""
+    s_off = -(-M // 16) * 16
+    return s_off, s_off + -(-M // MX_BLOCK)
+
+
+def check_downlink(downlink) -> None:
+    """``downlink`` is None (the fp32 average, as ever) or ``"mxfp8"`` (the average encoded to MXFP8 by
+    the aggregator); anything else is a ``ValueError``."""
+    if downlink is not None and downlink != "mxfp8":
+        raise ValueError(f"downlink must be None or 'mxfp8', not {downlink!r}")
 
 
 def native_byte_order(rows):
@@ -944,15 +958,21 @@ class AggregationEngine:
         return (K + (2 if R == BF16 else 1)) * ld * R.itemsize
 
     def fedavg_routed(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
-                      wire: bool = False) -> List[np.ndarray]:
+                      wire: bool = False, downlink: Optional[str] = None) -> List[np.ndarray]:
         """What the strategies call: :meth:`fedavg`, except that uniformly ``wire.BF16`` updates
         whose buckets exceed the budget are streamed through the GPU in parameter ranges
         (``MultiDeviceEngine.fedavg_routed`` with this one device) where :meth:`fedavg` refuses
-        them; that refusal is pinned by tests, so the route is this name."""
+        them; that refusal is pinned by tests, so the route is this name.  ``downlink="mxfp8"``: the
+        average of MXFP8 or MXFP4 updates comes back encoded to MXFP8 (:meth:`fedavg_mxfp8`); with
+        clients that sent no MX updates it is a ``NotImplementedError`` before any device work."""
+        check_downlink(downlink)
         if parameters_updates and any(has_mxfp4(pu) for pu in parameters_updates):
-            return self.fedavg_mxfp4(parameters_updates, n_samples, wire)  # ahead of MXFP8: both carry wire.E8M0
+            return self.fedavg_mxfp4(parameters_updates, n_samples, wire, downlink)  # ahead of MXFP8: both carry wire.E8M0
         if parameters_updates and any(has_mxfp8(pu) for pu in parameters_updates):
-            return self.fedavg_mxfp8(parameters_updates, n_samples, wire)  # the MXFP8 wire (DESIGN §2)
+            return self.fedavg_mxfp8(parameters_updates, n_samples, wire, downlink)  # the MXFP8 wire (DESIGN §2)
+        if downlink is not None:
+            raise NotImplementedError(f"FedAvg engine: downlink={downlink!r} encodes the average of MXFP8 or MXFP4 "
+                                      "updates; these clients sent none (accelerate_algo(..., wire='mxfp8'))")
         if (parameters_updates and parameters_updates[0]
                 and all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
             out = self._fedavg_bf16_out_of_core(parameters_updates, n_samples, wire)
@@ -973,13 +993,14 @@ class AggregationEngine:
 
     # ----------------------------------------------------------------------------------
     def fedavg_mxfp4(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
-                     wire: bool = False) -> List[np.ndarray]:
+                     wire: bool = False, downlink: Optional[str] = None) -> List[np.ndarray]:
         """FedAvg over MXFP4 updates (``[codes, scales, shapes]`` per client: ``wire.E2M1X2`` packed
         codes, ``wire.E8M0`` scales and the ``int64`` shape table): bit-identical to fed_avg.py:217-222
         on the exactly decoded fp32 inputs (``wire.mxfp4_to_float32``).  The K code rows and the K
         scale rows are staged as two byte buckets, ``fedagg_mx4_fedavg_e2m1`` reduces them in one
         call and the L fp32 layers come home (``wire``: as :class:`wire.BucketArray` layers of one
-        bucket).
+        bucket).  ``downlink="mxfp8"``: the result is the MXFP8 form :meth:`fedavg_mxfp8` gives with it
+        (the average is not packed to 4 bits), from the same fused kernel with its e2m1 decoder.
 
         Refused before any device work: clients of which only some are MXFP4
         (``NotImplementedError``), an update that is not the three arrays or whose code or scale
@@ -989,6 +1010,7 @@ class AggregationEngine:
         route)."""
         from . import _native_mx4
 
+        check_downlink(downlink)
         K = len(parameters_updates)
         n_mx = sum(1 for pu in parameters_updates if has_mxfp4(pu))
         if n_mx != K:
@@ -1006,18 +1028,17 @@ class AggregationEngine:
                                       f"{_native_mx4.MAX_PAIRWISE_K} clients (got {K})")
         if handoff.enabled():
             raise NotImplementedError("FedAvg engine: the device hand-off has no MXFP4 route")
-        return self._fedavg_mxfp4(parameters_updates, n_samples, wire, layout, M)
+        return self._fedavg_mxfp4(parameters_updates, n_samples, wire, layout, M, downlink)
 
     @serialized
-    def _fedavg_mxfp4(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, M: int):
+    def _fedavg_mxfp4(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, M: int, downlink=None):
         from . import _native_mx4
 
         t_start = time.perf_counter()
         K = len(parameters_updates)
         ld_c = -(-(-(-M // 2)) // 256) * 256  # code bytes per row: 16-B aligned rows
         ld_s = -(-(-(-M // MX_BLOCK)) // 256) * 256
-        need = K * (ld_c + ld_s) + 4 * layout.ld
-        slots = (self._B_BUCKET, self._B_CV, self._B_OUT)
+        need, slots = self._mx_need(K, ld_c + ld_s, layout.ld, M, downlink)
         if self.max_bucket_bytes is not None:
             budget = int(self.max_bucket_bytes)
         else:
@@ -1041,26 +1062,44 @@ class AggregationEngine:
         tm["prestaged"] = False
         tm["layout"] = "rows"
         tm["stage_s"] = time.perf_counter() - t0
-        d_out = s.buffer(self._B_OUT, layout.ld * 4)
         t1 = time.perf_counter()
-        _native_mx4.fedavg_e2m1([d_codes + k * ld_c for k in range(K)], [d_scales + k * ld_s for k in range(K)],
-                                fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx, d_out, s.stream)
-        out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp4")
-        s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
-        tm["kernel_fetch_s"] = time.perf_counter() - t1
-        results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+        rows = ([d_codes + k * ld_c for k in range(K)], [d_scales + k * ld_s for k in range(K)],
+                fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx)
+        if downlink:  # the result is the MXFP8 wire form whatever ``wire`` says
+            from ._native_mxdl import E2M1
+
+            res = self._mx_downlink(s, tm, E2M1, rows, [g.shape for g in layout.segments], "fedavg-mxfp4-down",
+                                    _native_mx4.fedavg_e2m1)
+            tm["kernel_fetch_s"] = time.perf_counter() - t1
+        else:
+            d_out = s.buffer(self._B_OUT, layout.ld * 4)
+            _native_mx4.fedavg_e2m1(*rows, d_out, s.stream)
+            out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp4")
+            s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+            tm["kernel_fetch_s"] = time.perf_counter() - t1
+            results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+            res = [results[li] for li in range(len(results))]
         tm.update({f"native_{k}": v for k, v in s.timing().items()})
         tm["total_s"] = time.perf_counter() - t_start
-        return [results[li] for li in range(len(results))]
+        return res
 
     # ----------------------------------------------------------------------------------
     def fedavg_mxfp8(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
-                     wire: bool = False) -> List[np.ndarray]:
+                     wire: bool = False, downlink: Optional[str] = None) -> List[np.ndarray]:
         """FedAvg over MXFP8 updates (``[layer_0 .. layer_{L-1}, scales]``, ``wire.E4M3`` layers and
         one trailing ``wire.E8M0`` array per client): bit-identical to fed_avg.py:217-222 on the
         exactly decoded fp32 inputs (``wire.mxfp8_to_float32``).  The K code rows and the K scale
         rows are staged as two byte buckets, ``fedagg_mx_fedavg_e4m3`` reduces them in one call and
         the L fp32 layers come home (``wire``: as :class:`wire.BucketArray` layers of one bucket).
+
+        ``downlink="mxfp8"`` (None: nothing changes): the rows are staged as above, then ONE
+        ``fedagg_mxdl_fedavg`` call averages them and encodes the average in the same pass, bit for
+        bit ``wire.float32_to_mxfp8`` of the fp32 result above; codes and scales come home in one
+        fetch, and the result has the uplink's form, ``[layer_0 .. layer_{L-1}`` as ``wire.E4M3``,
+        one ``wire.E8M0`` array``]``, all :class:`wire.BucketArray` views of that one buffer
+        (``last_timing["downlink"] = "mxfp8-fused"``).  Beyond the fused kernel's client table the
+        fp32 kernel runs into its slot and ``fedagg_mx_quantize`` encodes it there: the same bits,
+        ``"mxfp8-two-step"``.  The downlink carries no residual.
 
         Refused before any device work: clients of which only some are MXFP8
         (``NotImplementedError``), a scale array that is missing or has the wrong dtype or length,
@@ -1069,6 +1108,7 @@ class AggregationEngine:
         the in-core budget (``NotImplementedError``, each naming its route)."""
         from . import _native_mx
 
+        check_downlink(downlink)
         K = len(parameters_updates)
         n_mx = sum(1 for pu in parameters_updates if has_mxfp8(pu))
         if n_mx != K:
@@ -1086,18 +1126,18 @@ class AggregationEngine:
                                       f"{_native_mx.MAX_PAIRWISE_K} clients (got {K})")
         if handoff.enabled():
             raise NotImplementedError("FedAvg engine: the device hand-off has no MXFP8 route")
-        return self._fedavg_mxfp8(parameters_updates, n_samples, wire, layout, shapes, M)
+        return self._fedavg_mxfp8(parameters_updates, n_samples, wire, layout, shapes, M, downlink)
 
     @serialized
-    def _fedavg_mxfp8(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, shapes, M: int):
+    def _fedavg_mxfp8(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, shapes, M: int,
+                      downlink=None):
         from . import _native_mx
 
         t_start = time.perf_counter()
         K = len(parameters_updates)
         n_scales = -(-M // MX_BLOCK)
         ld_s = -(-n_scales // 256) * 256
-        need = K * (layout.ld + ld_s) + 4 * layout.ld
-        slots = (self._B_BUCKET, self._B_CV, self._B_OUT)
+        need, slots = self._mx_need(K, layout.ld + ld_s, layout.ld, M, downlink)
         if self.max_bucket_bytes is not None:
             budget = int(self.max_bucket_bytes)
         else:
@@ -1126,19 +1166,69 @@ class AggregationEngine:
         tm["prestaged"] = False
         tm["layout"] = "rows"
         tm["stage_s"] = time.perf_counter() - t0
-        d_out = s.buffer(self._B_OUT, layout.ld * 4)
         t1 = time.perf_counter()
-        _native_mx.fedavg_e4m3([d_codes + k * layout.ld for k in range(K)], [d_scales + k * ld_s for k in range(K)],
-                               fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx, d_out, s.stream)
-        out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp8")
-        s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
-        tm["kernel_fetch_s"] = time.perf_counter() - t1
-        results: List[Optional[np.ndarray]] = [None] * len(shapes)
-        for li, arr in BucketLayout(range(len(shapes)), shapes, np.float32).unpack(out, wire):
-            results[li] = arr
+        rows = ([d_codes + k * layout.ld for k in range(K)], [d_scales + k * ld_s for k in range(K)],
+                fedavg_weights(n_samples, "f32"), M, layout.pairwise_idx)
+        if downlink:  # the result is the MXFP8 wire form whatever ``wire`` says
+            from ._native_mxdl import E4M3 as IN_E4M3
+
+            results = self._mx_downlink(s, tm, IN_E4M3, rows, shapes, "fedavg-mxfp8-down", _native_mx.fedavg_e4m3)
+            tm["kernel_fetch_s"] = time.perf_counter() - t1
+        else:
+            d_out = s.buffer(self._B_OUT, layout.ld * 4)
+            _native_mx.fedavg_e4m3(*rows, d_out, s.stream)
+            out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-mxfp8")
+            s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+            tm["kernel_fetch_s"] = time.perf_counter() - t1
+            results: List[Optional[np.ndarray]] = [None] * len(shapes)
+            for li, arr in BucketLayout(range(len(shapes)), shapes, np.float32).unpack(out, wire):
+                results[li] = arr
         tm.update({f"native_{k}": v for k, v in s.timing().items()})
         tm["total_s"] = time.perf_counter() - t_start
         return results  # type: ignore[return-value]
+
+    def _mx_need(self, K: int, row_bytes: int, ld: int, M: int, downlink):
+        """(device bytes an MX call allocates, the session slots it reuses): the K staged rows, then
+        the fp32 slot -- or with ``downlink`` the encoded average, and the fp32 slot only on the
+        two-step route."""
+        from . import _native_mxdl
+
+        need, slots = K * row_bytes, [self._B_BUCKET, self._B_CV]
+        if downlink:
+            need += mx_downlink_bytes(M)[1]
+            slots.append(self._B_TMP)
+        if not downlink or K > _native_mxdl.KMAX:
+            need += 4 * ld
+            slots.append(self._B_OUT)
+        return need, tuple(slots)
+
+    def _mx_downlink(self, s, tm: dict, in_kind: int, rows, shapes, tag: str, fp32_fedavg) -> List[np.ndarray]:
+        """The MXFP8-encoded average of the staged MX ``rows`` (code addresses, scale addresses,
+        weights, M, numel == 1 indices): one fused ``fedagg_mxdl_fedavg`` call up to its client table,
+        else ``fp32_fedavg`` (the route's own kernel) into the fp32 slot and ``fedagg_mx_quantize``.
+        Codes and scales share one device buffer, the scales from the next multiple of 16 bytes so
+        that the kernel stores them wide, and come home in one fetch; the up to 15 bytes between
+        them are no part of the result."""
+        from . import _native_mx, _native_mxdl
+
+        M = rows[3]
+        n_scales = -(-M // MX_BLOCK)
+        s_off, total = mx_downlink_bytes(M)
+        d_q = s.buffer(self._B_TMP, total)
+        if len(rows[0]) <= _native_mxdl.KMAX:
+            _native_mxdl.fedavg(in_kind, *rows, d_q, d_q + s_off, s.stream)
+            tm["downlink"] = "mxfp8-fused"
+        else:
+            d_out = s.buffer(self._B_OUT, 4 * M)
+            fp32_fedavg(*rows, d_out, s.stream)
+            _native_mx.quantize(d_out, _native.FEDAGG_F32, M, d_q, d_q + s_off, s.stream)
+            tm["downlink"] = "mxfp8-two-step"
+        host = runtime.reusable_host_array(total, np.dtype(np.uint8), tag)
+        s.fetch(d_q, host)  # stream-ordered after the kernels; returns when the data is home
+        shapes = [tuple(sh) for sh in shapes]
+        pad = [(s_off - M,)] if s_off > M else []
+        views = bucket_views(host, shapes + pad + [(n_scales,)], [E4M3] * len(shapes) + [np.uint8] * len(pad) + [E8M0])
+        return views[:len(shapes)] + views[-1:]  # without the padding
 
     # ----------------------------------------------------------------------------------
     @mxfp4_first

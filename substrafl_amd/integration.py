@@ -52,7 +52,7 @@ from typing import Optional
 import numpy as np
 
 from . import handoff
-from .engine import Devices, engine_for
+from .engine import Devices, check_downlink, engine_for
 from .strategies.fed_avg import check_same_shapes, weighted_average
 from .strategies.fed_pca import orthonormal_layers
 from .strategies.scaffold import Scaffold as _MirrorScaffold
@@ -81,7 +81,8 @@ def _check_solve(solve: str) -> str:
     return solve
 
 
-def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host"):
+def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host",
+               downlink: Optional[str] = None):
     """A subclass of the reference strategy class ``strategy_cls`` (``FedAvg``, ``Scaffold``,
     ``FedPCA``, ``NewtonRaphson`` or a subclass of one of them) whose aggregation methods run on the
     engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
@@ -92,8 +93,12 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
     ``FEDAGG_NR_SOLVE=cholesky|device|host`` overrides it, read when the aggregation runs.  ``qr``
     matters for FedPCA only: ``"host"`` (the default) keeps the reference's ``np.linalg.qr`` of each
     averaged matrix, bit for bit; ``"device"`` orthonormalises each one on the GPU (:func:`strategies.fed_pca.orthonormal_layers`).  ``FEDAGG_PCA_QR=device|host``
-    overrides it, read when the aggregation runs."""
+    overrides it, read when the aggregation runs.  ``downlink`` is FedAvg's alone (a ``TypeError``
+    for the others, any string but ``"mxfp8"`` a ``ValueError``): ``"mxfp8"`` sends the average of
+    clients on the MXFP8 or MXFP4 wire back encoded to MXFP8
+    (:meth:`engine.AggregationEngine.fedavg_mxfp8`); None, the default, changes nothing."""
     _check_solve(solve)
+    check_downlink(downlink)
     if qr not in ("host", "device"):
         raise ValueError(f"qr must be 'host' or 'device', not {qr!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
@@ -104,6 +109,9 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
         base_init(self, *args, **kwargs)
         handoff.register("aggregator", self)  # the clients' exports are recorded for it (handoff.py)
 
+    if downlink is not None and (issubclass(strategy_cls, (strategies.Scaffold, strategies.FedPCA))
+                                 or not issubclass(strategy_cls, strategies.FedAvg)):
+        raise TypeError(f"downlink is an option of FedAvg, not of {strategy_cls.__name__}")
     ns = {"__doc__": f"{strategy_cls.__name__} with its aggregation on MI355X (substrafl_amd.integration).",
           "__init__": __init__,
           "_fedagg_device": device,
@@ -147,9 +155,10 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
         def avg_shared_states(self, shared_states):
             """fed_avg.py:176-224 on the engine."""
             out = weighted_average(shared_states, "FedAvgSharedState", self._fedagg_device, wire=False,
-                                   empty_error=empty)
+                                   empty_error=empty, downlink=self._fedagg_downlink)
             return averaged_cls(avg_parameters_update=out)
 
+        ns["_fedagg_downlink"] = downlink
         ns["avg_shared_states"] = remote(avg_shared_states)
         ns["_aggregation_methods"] = {"avg_shared_states": "fedavg"}
     elif getattr(strategies, "NewtonRaphson", None) is not None and issubclass(strategy_cls, strategies.NewtonRaphson):

@@ -35,7 +35,7 @@ import numpy as np
 
 from . import _native, runtime
 from .engine import (KIND_CODES, TILED_KINDS, AggregationEngine, FedAvgPlan, ScaffoldBucketPlan, ScaffoldPlan,
-                     TiledFedAvgPlan, bucket_dtype16, direct_rows, equal_count, fedavg_weights, kind_of,
+                     TiledFedAvgPlan, bucket_dtype16, check_downlink, direct_rows, equal_count, fedavg_weights, kind_of,
                      native_byte_order, reject_bf16, reject_mxfp8, scaffold_bucket_dtypes, scaffold_weights, serialized, tiled_elems,
                      tiled_recommended, tiled_tile)
 from .layout import ROW_ALIGN_BYTES, BucketLayout
@@ -356,13 +356,18 @@ class MultiDeviceEngine:
         return results  # type: ignore[return-value]
 
     def fedavg_routed(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
-                      wire: bool = False) -> List[np.ndarray]:
+                      wire: bool = False, downlink: Optional[str] = None) -> List[np.ndarray]:
         """What the strategies call: :meth:`fedavg`, and for updates that are uniformly
         ``wire.BF16`` the same sharded plan over 2-byte rows with an fp32 result (each sub-range one
         ``fedagg_fedavg_bf16`` / ``_tiled_bf16`` launch, ``K * 2 + 4`` bytes of HBM per element), bit-
         identical to :class:`engine.AggregationEngine` on one GPU.  :meth:`fedavg` itself keeps
-        refusing ``wire.BF16`` (its refusal is pinned by tests), so the route is this name."""
+        refusing ``wire.BF16`` (its refusal is pinned by tests), so the route is this name.  This
+        route has no MX path, so it has no MXFP8 ``downlink`` either: a ``NotImplementedError``."""
+        check_downlink(downlink)
         reject_mxfp8(parameters_updates, "MultiDeviceEngine.fedavg_routed (several devices, or out of core)")
+        if downlink is not None:
+            raise NotImplementedError(f"MultiDeviceEngine.fedavg_routed (several devices, or out of core): no "
+                                      f"downlink={downlink!r} route (FedAvg on one GPU, in core, encodes the average)")
         if (not parameters_updates or not parameters_updates[0]
                 or not all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
             return self.fedavg(parameters_updates, n_samples, wire)

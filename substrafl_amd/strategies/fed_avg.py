@@ -11,7 +11,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ..engine import Devices, engine_for
+from ..engine import Devices, check_downlink, engine_for
 from ..exceptions import EmptySharedStatesError
 from ..remote import remote
 from ..schemas import FedAvgAveragedState, FedAvgSharedState, StrategyName
@@ -32,14 +32,19 @@ def check_same_shapes(per_client_layers: List[List[np.ndarray]]) -> None:
 
 
 class FedAvg(Strategy):
-    """Federated averaging: ``Δw = Σ_k (n_k / n) Δw_k`` (fed_avg.py:23-52)."""
+    """Federated averaging: ``Δw = Σ_k (n_k / n) Δw_k`` (fed_avg.py:23-52).
 
-    def __init__(self, algo, metric_functions=None, device: Devices = None):
-        if device is None:
-            super().__init__(algo=algo, metric_functions=metric_functions)
-        else:
-            super().__init__(algo=algo, metric_functions=metric_functions, device=device)
+    ``downlink="mxfp8"`` (None, the default, changes nothing; any other string is a ``ValueError``):
+    the average of clients on the MXFP8 or MXFP4 wire goes back to them encoded to MXFP8, 1.03 bytes
+    per parameter instead of 4 (:meth:`engine.AggregationEngine.fedavg_mxfp8`); their
+    ``weight_manager.increment_parameters`` decodes it on the device.  It carries no residual."""
+
+    def __init__(self, algo, metric_functions=None, device: Devices = None, downlink: Optional[str] = None):
+        check_downlink(downlink)
+        extra = {k: v for k, v in (("device", device), ("downlink", downlink)) if v is not None}
+        super().__init__(algo=algo, metric_functions=metric_functions, **extra)  # recorded only when given
         self._device = device
+        self._downlink = downlink
         self._local_states = None
         self._shared_states = None
 
@@ -58,16 +63,17 @@ class FedAvg(Strategy):
             ValueError: a layer's shape differs between clients (``np.sum``, fed_avg.py:222).
             pydantic.ValidationError: a 0-d layer (its average is a scalar, schemas.py:29).
         """
-        averaged_states = weighted_average(shared_states, "FedAvgSharedState", self._device)
+        averaged_states = weighted_average(shared_states, "FedAvgSharedState", self._device, downlink=self._downlink)
         return FedAvgAveragedState(avg_parameters_update=averaged_states)
 
 
 def weighted_average(shared_states, state_name: str, device: Devices = None, wire: bool = True,
-                     empty_error=EmptySharedStatesError) -> List[np.ndarray]:
+                     empty_error=EmptySharedStatesError, downlink: Optional[str] = None) -> List[np.ndarray]:
     """fed_avg.py:207-222 (also fed_pca.py:244-257): validation on the host, the weighted sum
     of every layer on the GPU.  ``wire``: layers in the flat wire format (this package's own
     schemas); False: plain NumPy arrays (the reference's schemas, :mod:`substrafl_amd.integration`).
-    ``empty_error``: the exception class raised for an empty list (the reference's own there)."""
+    ``empty_error``: the exception class raised for an empty list (the reference's own there).
+    ``downlink``: FedAvg's option, passed to the engine's ``fedavg_routed`` when set."""
     if len(shared_states) == 0:
         raise empty_error(
             "Your shared_states is empty. Please ensure that "
@@ -90,4 +96,6 @@ def weighted_average(shared_states, state_name: str, device: Devices = None, wir
     # substrafl_amd's own schemas already need this package to unpickle: the flat wire format.
     # fedavg_routed where the engine has it: fedavg, plus wire.BF16 states on the multi-GPU and
     # out-of-core routes, which fedavg itself refuses
+    if downlink is not None:
+        return engine.fedavg_routed(updates, n_samples, wire=wire, downlink=downlink)
     return getattr(engine, "fedavg_routed", engine.fedavg)(updates, n_samples, wire=wire)
