@@ -68,6 +68,8 @@ def _reference_base(algo_cls):
 
 
 def _export(self, tensors, tag="export"):
+    if getattr(self, "_fedagg_topk", False):  # the residual is part of the wire: never without it
+        return wm.export_topk(tensors, self._fedagg_topk_density, _mx_residual(self, tensors), tag=tag)
     if getattr(self, "_fedagg_mxfp4", False):
         residual = _mx_residual(self, tensors) if getattr(self, "_fedagg_error_feedback", False) else None
         return wm.export_mxfp4(tensors, tag=tag, residual=residual)
@@ -304,7 +306,7 @@ def _registering_init(base_init):
     return __init__
 
 
-def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feedback: bool = False):
+def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feedback: bool = False, density=None):
     """A subclass of ``algo_cls`` (SubstraFL's ``TorchFedAvgAlgo`` / ``TorchScaffoldAlgo`` /
     ``TorchNewtonRaphsonAlgo`` or a subclass of one) whose ``train`` moves weights with the
     flat-bucket kernels.  ``wire``: ``True`` exports :class:`..wire.BucketArray` layers instead of plain
@@ -320,6 +322,13 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
     residual of 4 bytes per parameter in ``_fedagg_mx_residual`` (device memory, and the checkpoint
     key ``"fedagg_mx_residual"``), and adds it to the next round's update before quantising, in one
     fused kernel (``libfedagg_mxef.so``, include/fedagg_mxef.h); the wire format does not change.
+    ``wire="topk"`` (FedAvg only, refused in the same ways) sends the largest magnitudes of the update
+    as (index, value) pairs (:func:`.weight_manager.export_topk`: an exact selection with every tie
+    kept, 8 bytes per sent element, three arrays in one buffer; ``libfedagg_topk.so``,
+    include/fedagg_topk.h).  ``density`` (only with ``wire="topk"``, a ``TypeError`` otherwise; default
+    0.01, outside (0, 1] a ``ValueError``) is the share of the elements sent, and
+    ``error_feedback=True`` is required with it (a ``ValueError`` without): everything else stays in
+    the same residual and checkpoint key.  The aggregator's average comes back dense.
     ``hessian_check`` (NewtonRaphson only; a ``TypeError`` for the others): ``"host"``, the
     default, keeps the reference's eigenvalue check and never loads the dense library;
     ``"device"`` tries a Cholesky certificate on the GPU first
@@ -327,12 +336,23 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
     ``train`` runs)."""
     base = _reference_base(algo_cls)
     kind = _BASES[base.__name__]
-    if isinstance(wire, str) and wire not in ("mxfp8", "mxfp4"):
-        raise ValueError(f"wire must be True, False or 'mxfp8' (or 'mxfp4', the 4-bit wire), not {wire!r}")
-    mxfp8, mxfp4 = wire == "mxfp8", wire == "mxfp4"
-    if (mxfp8 or mxfp4) and kind != "fedavg":
+    if isinstance(wire, str) and wire not in ("mxfp8", "mxfp4", "topk"):
+        raise ValueError(f"wire must be True, False or 'mxfp8' (or 'mxfp4', the 4-bit wire, or 'topk', the sparse "
+                         f"wire), not {wire!r}")
+    mxfp8, mxfp4, topk = wire == "mxfp8", wire == "mxfp4", wire == "topk"
+    if (mxfp8 or mxfp4 or topk) and kind != "fedavg":
         raise TypeError(f"wire={wire!r} is an option of TorchFedAvgAlgo, not of {base.__name__}")
-    if error_feedback and not (mxfp8 or mxfp4):
+    if density is not None and not topk:
+        raise TypeError(f"density is an option of wire='topk' (TorchFedAvgAlgo), not of wire={wire!r} on "
+                        f"{base.__name__}")
+    if topk:
+        if not error_feedback:
+            raise ValueError("wire='topk' needs error_feedback=True: sparsification without the residual discards "
+                             "most of every update")
+        density = 0.01 if density is None else density
+        if isinstance(density, bool) or not isinstance(density, (int, float)) or not 0.0 < density <= 1.0:
+            raise ValueError(f"density must be in (0, 1], not {density!r}")
+    if error_feedback and not (mxfp8 or mxfp4 or topk):
         raise TypeError(f"error_feedback is an option of wire='mxfp8' (TorchFedAvgAlgo), not of wire={wire!r} on "
                         f"{base.__name__}")
     if kind != "newton_raphson" and hessian_check is not None:
@@ -362,6 +382,8 @@ def accelerate_algo(algo_cls, wire: bool = False, hessian_check=None, error_feed
         ns["_scaffold_parameters_update"] = _scaffold_parameters_update
     else:
         ns["train"] = remote_data(_fedavg_train(schemas.FedAvgSharedState))
+    if topk:  # only then, like the residual below
+        ns.update({"_fedagg_topk": True, "_fedagg_topk_density": float(density)})
     if error_feedback:  # only then: every other class stays attribute for attribute what it is
         cell, get_state, update_from = _checkpoint_methods()
         ns.update({"_fedagg_error_feedback": True, "_fedagg_mx_residual": None,

@@ -543,6 +543,69 @@ def export_mxfp4(tensors: Sequence[torch.Tensor], tag: str = "export", residual:
     return [c, s, t]
 
 
+def export_topk(tensors: Sequence[torch.Tensor], density: float, residual: torch.Tensor, tag: str = "export"
+                ) -> List[np.ndarray]:
+    """The top-k form of ``tensors`` (``wire.py``: ``[indices, values, shapes]``, ``wire.TOPK_IDX``
+    flat indices in ascending order, the ``wire.TOPK_VAL`` fp32 values at them and the ``int64`` shape
+    table): the ``k = max(1, min(M, ceil(density M)))`` largest magnitudes of ``fl32(x + residual)``,
+    every tie at the threshold included, selected on the device by ``fedagg_topk_select`` from the
+    flat fp32 or bf16 bucket and compacted in index order by ``fedagg_topk_compact``
+    (``libfedagg_topk.so``, loaded only here and by the aggregator's top-k route).  Between the two
+    the host reads nnz, the one added synchronisation.  Indices and values share one device buffer,
+    so they leave in ONE D2H copy into one host buffer that also holds the shape table, and the
+    three arrays returned are :class:`wire.BucketArray` views of it.
+
+    ``residual`` is not optional: a contiguous fp32 tensor of M elements on the bucket's device,
+    overwritten with what was not sent (+0.0 where an element was sent or is not finite); any other
+    dtype, device, layout or size, or a ``density`` outside (0, 1], is a ``ValueError`` before any
+    device work.  Anything but fp32 or bf16 tensors on a ROCm device is refused
+    (``NotImplementedError``), as :func:`export_mxfp4` refuses it."""
+    from .. import _native_topk, runtime
+    from ..wire import TOPK_IDX, TOPK_VAL, mxfp4_shape_table
+
+    tensors = list(tensors)
+    kind = _kind(tensors)
+    if kind not in (_native.FEDAGG_F32, _native.FEDAGG_BF16):
+        dts = sorted({str(t.dtype) for t in tensors})
+        raise NotImplementedError(f"wire='topk': the update of an fp32 or bf16 model on a ROCm device is sparsified, "
+                                  f"got {dts} on {sorted({str(t.device) for t in tensors})}")
+    if not 0.0 < float(density) <= 1.0:
+        raise ValueError(f"export_topk: density must be in (0, 1], got {density!r}")
+    M = sum(t.numel() for t in tensors)
+    if not isinstance(residual, torch.Tensor) or residual.dtype != torch.float32 or not residual.is_contiguous():
+        raise ValueError("export_topk: residual must be a contiguous float32 tensor, got "
+                         f"{getattr(residual, 'dtype', type(residual).__name__)}")
+    if residual.device != tensors[0].device:
+        raise ValueError(f"export_topk: residual is on {residual.device}, the bucket on {tensors[0].device}")
+    if residual.numel() != M:
+        raise ValueError(f"export_topk: residual holds {residual.numel()} elements, the bucket {M}")
+    if M >= 1 << 32:
+        raise ValueError(f"export_topk: {M} elements, the 4-byte indices reach below 2**32")
+    flat = flat_bucket(tensors)
+    if flat is None:
+        flat = _gather_flat(tensors)
+    table = mxfp4_shape_table([tuple(t.shape) for t in tensors])
+    k = max(1, min(M, int(np.ceil(float(density) * M))))
+    stream = _stream(flat.device)
+    ws_bytes = _native_topk.workspace(M)[0]
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=flat.device)
+    state = torch.empty(_native_topk.STATE_WORDS, dtype=torch.int32, device=flat.device)
+    _native_topk.select(kind, flat.data_ptr(), residual.data_ptr(), M, k, ws.data_ptr(), ws_bytes, state.data_ptr(), stream)
+    nnz = int(state.cpu()[_native_topk.STATE_NNZ].item()) & 0xFFFFFFFF  # the one read between the two calls
+    dev = torch.empty(max(1, 8 * nnz), dtype=torch.uint8, device=flat.device)  # the indices, then the values
+    _native_topk.compact(residual.data_ptr(), M, ws.data_ptr(), state.data_ptr(), nnz, dev.data_ptr(),
+                         dev.data_ptr() + 4 * nnz, stream)
+    # one host buffer: the shape table first (8-B aligned), then the indices and the values as they left the device
+    host = runtime.reusable_host_array(table.nbytes + 8 * nnz, np.dtype(np.uint8), tag)
+    host[: table.nbytes] = table.view(np.uint8)
+    torch.cuda.current_stream(flat.device).synchronize()  # the compaction ran on torch's stream
+    if nnz:
+        with runtime.device_lock(flat.device.index):  # the session's ring is shared with the engine
+            runtime.session(flat.device.index).fetch(dev.data_ptr(), host[table.nbytes :])
+    t, i, v = bucket_views(host, [(table.size,), (nnz,), (nnz,)], [np.dtype(np.int64), TOPK_IDX, TOPK_VAL])
+    return [i, v, t]
+
+
 def export_numpy(tensors: Sequence[torch.Tensor], wire: bool = True, tag: str = "export") -> List[np.ndarray]:
     """``[p.cpu().detach().numpy() for p in ...]`` (torch_fed_avg_algo.py:227-230) with ONE D2H copy
     when the tensors are views of one flat bucket.  With ``wire`` the arrays returned are

@@ -38,8 +38,8 @@ import numpy as np
 
 from . import _native, handoff, runtime
 from .layout import BucketLayout
-from .wire import (BF16, E2M1X2, E4M3, E8M0, MX_BLOCK, bucket_views, flat_of, has_mxfp4, has_mxfp8, mxfp4_check,
-                   mxfp4_layer_shapes, mxfp8_check)
+from .wire import (BF16, E2M1X2, E4M3, E8M0, MX_BLOCK, TOPK_IDX, TOPK_VAL, bucket_views, flat_of, has_mxfp4, has_mxfp8,
+                   has_topk, mxfp4_check, mxfp4_layer_shapes, mxfp8_check, topk_check)
 
 KINDS = ("f32", "bf16", "f64", "f16")
 BF16_GROUP = "bf16"  # fedavg()'s dtype-group key of wire.BF16 layers (the others are NumPy dtype strings)
@@ -95,7 +95,13 @@ def reject_mxfp8(rows, what: str) -> None:
     """MXFP8 updates (``wire.E4M3`` codes, ``wire.E8M0`` scales) hold bit patterns: only FedAvg on
     the single-GPU in-core route (:meth:`AggregationEngine.fedavg_mxfp8`) decodes them, every
     other route refuses them by name; so it is with MXFP4 updates (``wire.E2M1X2`` codes) and
-    :meth:`AggregationEngine.fedavg_mxfp4`."""
+    :meth:`AggregationEngine.fedavg_mxfp4`, and with top-k updates (``wire.TOPK_IDX`` indices) and
+    :meth:`AggregationEngine.fedavg_topk`."""
+    for row in rows:
+        for a in row:
+            if getattr(a, "dtype", None) in (TOPK_IDX, TOPK_VAL):
+                raise NotImplementedError(f"{what}: no top-k path for wire.TOPK_IDX / wire.TOPK_VAL arrays "
+                                          "(FedAvg on one GPU, in core, aggregates them)")
     for row in rows:
         for a in row:
             if getattr(a, "dtype", None) == E2M1X2:  # first: an MXFP4 update carries wire.E8M0 too
@@ -514,12 +520,22 @@ def c_mismatches16(c_rows) -> Tuple[int, str]:
     return mism, path
 
 
+def refuse_downlink(downlink) -> None:
+    """``downlink`` with clients that sent no MX updates: a ``NotImplementedError`` before any device work."""
+    if downlink is not None:
+        raise NotImplementedError(f"FedAvg engine: downlink={downlink!r} encodes the average of MXFP8 or MXFP4 "
+                                  "updates; these clients sent none (accelerate_algo(..., wire='mxfp8'))")
+
+
 def mxfp4_first(method):
-    """``AggregationEngine.fedavg`` with updates that carry ``wire.E2M1X2`` sent to
+    """``AggregationEngine.fedavg`` with updates that carry ``wire.TOPK_IDX`` sent to
+    :meth:`AggregationEngine.fedavg_topk` and those that carry ``wire.E2M1X2`` to
     :meth:`AggregationEngine.fedavg_mxfp4`, whose refusals come before any lock or device work."""
 
     @functools.wraps(method)
     def wrapper(self, parameters_updates, n_samples, wire=False):
+        if parameters_updates and any(has_topk(pu) for pu in parameters_updates):
+            return self.fedavg_topk(parameters_updates, n_samples, wire)
         if parameters_updates and any(has_mxfp4(pu) for pu in parameters_updates):
             return self.fedavg_mxfp4(parameters_updates, n_samples, wire)
         return method(self, parameters_updates, n_samples, wire)
@@ -966,13 +982,13 @@ class AggregationEngine:
         average of MXFP8 or MXFP4 updates comes back encoded to MXFP8 (:meth:`fedavg_mxfp8`); with
         clients that sent no MX updates it is a ``NotImplementedError`` before any device work."""
         check_downlink(downlink)
+        if parameters_updates and any(has_topk(pu) for pu in parameters_updates):
+            return self.fedavg_topk(parameters_updates, n_samples, wire, downlink)  # the top-k wire (DESIGN §2)
         if parameters_updates and any(has_mxfp4(pu) for pu in parameters_updates):
             return self.fedavg_mxfp4(parameters_updates, n_samples, wire, downlink)  # ahead of MXFP8: both carry wire.E8M0
         if parameters_updates and any(has_mxfp8(pu) for pu in parameters_updates):
             return self.fedavg_mxfp8(parameters_updates, n_samples, wire, downlink)  # the MXFP8 wire (DESIGN §2)
-        if downlink is not None:
-            raise NotImplementedError(f"FedAvg engine: downlink={downlink!r} encodes the average of MXFP8 or MXFP4 "
-                                      "updates; these clients sent none (accelerate_algo(..., wire='mxfp8'))")
+        refuse_downlink(downlink)
         if (parameters_updates and parameters_updates[0]
                 and all(np.asarray(a).dtype == BF16 for pu in parameters_updates for a in pu)):
             out = self._fedavg_bf16_out_of_core(parameters_updates, n_samples, wire)
@@ -990,6 +1006,97 @@ class AggregationEngine:
         out = ooc.fedavg_routed(parameters_updates, n_samples, wire)
         self.last_timing = {"out_of_core": ooc.last_timing, "staging": "out-of-core"}
         return out
+
+    # ----------------------------------------------------------------------------------
+    def fedavg_topk(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],
+                    wire: bool = False, downlink: Optional[str] = None) -> List[np.ndarray]:
+        """FedAvg over top-k updates (``[indices, values, shapes]`` per client: ``wire.TOPK_IDX``
+        ascending flat indices, the ``wire.TOPK_VAL`` values at them and the ``int64`` shape table):
+        bit-identical to fed_avg.py:217-222 on the densified fp32 inputs (``wire.topk_to_float32``),
+        which are never built.  The K sparse rows are staged into one byte bucket at 16-B aligned
+        offsets, ``fedagg_topk_fedavg`` reduces them in one call and the L dense fp32 layers come home
+        (``wire``: as :class:`wire.BucketArray` layers of one bucket).  The downlink stays dense.
+
+        Refused before any device work: clients of which only some are top-k, more clients than the
+        library's table takes, ``downlink`` (``NotImplementedError``), an update that is not the
+        three arrays, whose index and value arrays differ in length, or whose indices are not
+        ascending or not below M, shape tables that differ between clients (``ValueError``), the
+        device hand-off and buckets beyond the in-core budget (``NotImplementedError``, each naming
+        its route)."""
+        from . import _native_topk
+
+        check_downlink(downlink)
+        K = len(parameters_updates)
+        n_tk = sum(1 for pu in parameters_updates if has_topk(pu))
+        if n_tk != K:
+            raise NotImplementedError(f"FedAvg engine: {n_tk} of {K} clients sent top-k updates; the top-k route "
+                                      "takes top-k from every client or from none")
+        refuse_downlink(downlink)
+        if K > _native_topk.KMAX:
+            raise NotImplementedError(f"FedAvg engine: the top-k route takes up to {_native_topk.KMAX} clients "
+                                      f"(got {K})")
+        M = topk_check(parameters_updates[0])
+        for pu in parameters_updates[1:]:
+            topk_check(pu, table=parameters_updates[0][2])
+        shapes = mxfp4_layer_shapes(parameters_updates[0][2])
+        layout = BucketLayout(range(len(shapes)), shapes, np.float32)  # the fp32 result; its numel == 1 indices
+        if handoff.enabled():
+            raise NotImplementedError("FedAvg engine: the device hand-off has no top-k route")
+        nnz = [int(np.asarray(pu[0]).size) for pu in parameters_updates]
+        half = [-(-4 * n // 16) * 16 for n in nnz]  # a row: its indices, then its values from the next multiple of 16 B
+        offs = np.concatenate([[0], np.cumsum([2 * h for h in half])]).astype(np.int64)
+        need = int(offs[-1]) + _native_topk.fedavg_ws_bytes(M, K) + 4 * layout.ld  # the rows, the bounds, the result
+        if self.max_bucket_bytes is not None and need > int(self.max_bucket_bytes):
+            self._topk_past_budget(need)
+        return self._fedavg_topk(parameters_updates, n_samples, wire, layout, M, nnz, half, offs, need)
+
+    @staticmethod
+    def _topk_past_budget(need: int):
+        raise NotImplementedError(f"FedAvg engine: the out-of-core route has no top-k path ({need} bytes do "
+                                  "not fit the bucket budget)")
+
+    @serialized
+    def _fedavg_topk(self, parameters_updates, n_samples, wire: bool, layout: BucketLayout, M: int, nnz, half, offs,
+                     need: int):
+        from . import _native_topk
+
+        t_start = time.perf_counter()
+        K = len(parameters_updates)
+        if self.max_bucket_bytes is None:
+            from .multi_device import HBM_HEADROOM
+
+            slots = (self._B_BUCKET, self._B_WS, self._B_OUT)
+            if need > int((runtime.device_memory(self._index())[0] + self.session().held_bytes(slots)) * HBM_HEADROOM):
+                self._topk_past_budget(need)
+        s = self.session()
+        self.last_timing = tm = {}
+        self._prestaged = {}
+        seg = lambda a: np.ascontiguousarray(a).reshape(-1).view(np.uint8)  # noqa: E731
+
+        t0 = time.perf_counter()
+        d_rows = s.buffer(self._B_BUCKET, int(offs[-1]))
+        for k, pu in enumerate(parameters_updates):  # the rows differ in length: one staging call each, no host copy
+            if nnz[k]:
+                pad = [np.zeros(half[k] - 4 * nnz[k], np.uint8)] if half[k] > 4 * nnz[k] else []
+                s.stage(d_rows + int(offs[k]), 2 * half[k], [[seg(pu[0]), *pad, seg(pu[1])]])
+        tm["staging"] = "topk-host-rows"
+        tm["prestaged"] = False
+        tm["layout"] = "rows"
+        tm["stage_s"] = time.perf_counter() - t0
+        t1 = time.perf_counter()
+        fed_bytes = _native_topk.workspace(M, K)[1]
+        d_ws = s.buffer(self._B_WS, fed_bytes)
+        d_out = s.buffer(self._B_OUT, layout.ld * 4)
+        d_idx = [d_rows + int(offs[k]) for k in range(K)]
+        _native_topk.fedavg(d_idx, [d + h for d, h in zip(d_idx, half)], nnz, fedavg_weights(n_samples, "f32"), M,
+                            layout.pairwise_idx, d_ws, fed_bytes, d_out, s.stream)
+        out = runtime.reusable_host_array(M, np.dtype(np.float32), "fedavg-topk")
+        s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+        tm.update({f"native_{k}": v for k, v in s.timing().items()})
+        tm["total_s"] = time.perf_counter() - t_start
+        return [results[li] for li in range(len(results))]
 
     # ----------------------------------------------------------------------------------
     def fedavg_mxfp4(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],

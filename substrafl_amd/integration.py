@@ -319,12 +319,14 @@ def newton_raphson_hessian_check(hessian, l2_coeff, device: Optional[Devices] = 
     return route
 
 
-def accelerate_algo(algo_cls, wire: bool = False, hessian_check: Optional[str] = None, error_feedback: bool = False):
+def accelerate_algo(algo_cls, wire: bool = False, hessian_check: Optional[str] = None, error_feedback: bool = False,
+                    density: Optional[float] = None):
     """The client half: :func:`substrafl_amd.algorithms.accelerate.accelerate_algo`.
     Imported on call, so the aggregation side of this module never imports torch."""
     from .algorithms.accelerate import accelerate_algo as _accelerate_algo
 
-    return _accelerate_algo(algo_cls, wire=wire, hessian_check=hessian_check, error_feedback=error_feedback)
+    return _accelerate_algo(algo_cls, wire=wire, hessian_check=hessian_check, error_feedback=error_feedback,
+                            density=density)
 
 
 def scaffold_average(strategy, shared_states, aggregation_lr, device: Optional[Devices] = None, wire: bool = False):

@@ -15,6 +15,7 @@ from ..engine import Devices, check_downlink, engine_for
 from ..exceptions import EmptySharedStatesError
 from ..remote import remote
 from ..schemas import FedAvgAveragedState, FedAvgSharedState, StrategyName
+from ..wire import has_topk
 from .strategy import Strategy
 
 
@@ -91,7 +92,8 @@ def weighted_average(shared_states, state_name: str, device: Devices = None, wir
     if n_all_samples == 0:
         raise ZeroDivisionError("division by zero")
     updates = [list(state.parameters_update) for state in shared_states]
-    check_same_shapes(updates)
+    if not any(has_topk(u) for u in updates):  # top-k rows differ in length: the engine compares their shape tables
+        check_same_shapes(updates)
     engine = engine_for(device)
     # substrafl_amd's own schemas already need this package to unpickle: the flat wire format.
     # fedavg_routed where the engine has it: fedavg, plus wire.BF16 states on the multi-GPU and

@@ -393,6 +393,115 @@ def mxfp4_error_feedback(x, res):
         return codes, scales, np.where(keep, r - d, np.float32(0.0)).astype(np.float32)
 
 
+# ------------------------------------------------------------------------------------------
+# Top-k sparse: the largest magnitudes of the update as (index, value) pairs
+# (include/fedagg_topk.h states the same rule).
+#
+# A sparse update is three arrays, ``[indices, values, shapes]``: ``indices`` a 1-D :data:`TOPK_IDX`
+# array of nnz strictly ascending flat indices into the raveled concatenation of the layers,
+# ``values`` the 1-D :data:`TOPK_VAL` array of the nnz fp32 values at them, ``shapes`` the ``int64``
+# table of :func:`mxfp4_shape_table`.  M is below 2^32.
+#
+# The rule, all fp32: r = fl32(x + res); m = bits(r) & 0x7FFFFFFF as uint32 (NaN and Inf sort above
+# every finite value); t the k-th largest of m; kept are all i with m_i >= max(t, 1): every tie at
+# the threshold is kept, so nnz >= k unless fewer than k elements are non-zero, and zeros are never
+# sent.  The values are the kept r_i bit for bit; res'_i = +0.0 where i is kept or r_i is not
+# finite, r_i elsewhere.  k = max(1, min(M, ceil(density M))) is the caller's.
+#
+# Like BF16 these are structured dtypes NumPy refuses arithmetic on.
+TOPK_IDX = np.dtype([("topk_idx", "<u4")])
+TOPK_VAL = np.dtype([("topk_f32", "<f4")])
+
+
+def has_topk(parameters_update) -> bool:
+    """Whether any array of ``parameters_update`` carries :data:`TOPK_IDX` or :data:`TOPK_VAL`."""
+    return any(getattr(a, "dtype", None) in (TOPK_IDX, TOPK_VAL) for a in parameters_update)
+
+
+def is_topk(parameters_update) -> bool:
+    """Whether ``parameters_update`` has the top-k form ``[indices, values, shapes]`` by its dtypes
+    (lengths and indices are checked by :func:`topk_check`)."""
+    pu = list(parameters_update) if isinstance(parameters_update, (list, tuple)) else []
+    return len(pu) == 3 and [getattr(a, "dtype", None) for a in pu] == [TOPK_IDX, TOPK_VAL, np.dtype(np.int64)]
+
+
+def topk_check(parameters_update, table=None) -> int:
+    """M of a top-k update ``[indices, values, shapes]``; ``ValueError`` when it is not three arrays
+    of :data:`TOPK_IDX`, :data:`TOPK_VAL` and ``int64``, the index and value arrays are not 1-D of
+    one length, the indices are not strictly ascending or not below M, M is not below 2^32, or the
+    shape table differs from ``table`` (another client's)."""
+    pu = list(parameters_update)
+    if not is_topk(pu):
+        raise ValueError("top-k update: expected [indices (wire.TOPK_IDX), values (wire.TOPK_VAL), shapes (int64)], got "
+                         f"{[str(getattr(a, 'dtype', type(a).__name__)) for a in pu]}")
+    M = sum(int(np.prod(s, dtype=np.int64)) for s in mxfp4_layer_shapes(pu[2]))
+    if M >= 1 << 32:
+        raise ValueError(f"top-k update: {M} elements, the 4-byte indices reach below 2**32")
+    if table is not None and not np.array_equal(np.asarray(pu[2]), np.asarray(table)):
+        raise ValueError("top-k update: shape tables differ between clients")
+    i, v = np.asarray(pu[0]), np.asarray(pu[1])
+    if i.ndim != 1 or v.ndim != 1 or i.size != v.size:
+        raise ValueError(f"top-k update: indices and values must be 1-D of one length, got shapes {i.shape} and {v.shape}")
+    i = i["topk_idx"]
+    if i.size and int(i[-1]) >= M:
+        raise ValueError(f"top-k update: index {int(i[-1])} is not below the {M} elements of the shape table")
+    if i.size > 1 and not (i[1:] > i[:-1]).all():
+        raise ValueError("top-k update: the indices are not strictly ascending")
+    return M
+
+
+def topk_error_feedback(x, res, k: int):
+    """One error-feedback step of the rule above on the flat fp32 ``x`` and residual ``res``:
+    ``(indices, values, res')``."""
+    with np.errstate(all="ignore"):
+        r = (np.asarray(x, np.float32).reshape(-1) + np.asarray(res, np.float32).reshape(-1)).astype(np.float32)
+    M, k = r.size, int(k)
+    if M >= 1 << 32:
+        raise ValueError(f"top-k: {M} elements, the 4-byte indices reach below 2**32")
+    if M == 0:
+        return np.zeros(0, TOPK_IDX), np.zeros(0, TOPK_VAL), r
+    if not 1 <= k <= M:
+        raise ValueError(f"top-k: k must be in [1, {M}], got {k}")
+    m = r.view(np.uint32) & np.uint32(0x7FFFFFFF)
+    t = np.partition(m, M - k)[M - k]
+    kept = m >= max(t, np.uint32(1))
+    idx = np.flatnonzero(kept).astype(np.uint32)
+    new = np.where(kept | (m >= np.uint32(0x7F800000)), np.float32(0.0), r).astype(np.float32)
+    return idx.view(TOPK_IDX), r[kept].view(TOPK_VAL), new
+
+
+def float32_to_topk(x, k: int):
+    """``x`` (an array, or a list of layers; cast to fp32) sparsified by the rule above with a zero
+    residual: ``(indices, values, shapes)``, the three arrays of a top-k update."""
+    arrs = [np.asarray(a, dtype=np.float32) for a in (x if isinstance(x, (list, tuple)) else [x])]
+    flat = np.concatenate([a.reshape(-1) for a in arrs]) if arrs else np.zeros(0, np.float32)
+    idx, val, _ = topk_error_feedback(flat, np.zeros(flat.size, np.float32), k)
+    return idx, val, mxfp4_shape_table([a.shape for a in arrs])
+
+
+def topk_to_float32(indices, values, shapes):
+    """The dense fp32 form of a top-k update: the values at their indices, +0.0 elsewhere; a list
+    of layers shaped by the shape table ``shapes``, or, with ``shapes`` an int M, the flat array."""
+    indices, values = np.asarray(indices), np.asarray(values)
+    if indices.dtype != TOPK_IDX or values.dtype != TOPK_VAL:
+        raise TypeError("topk_to_float32: expected wire.TOPK_IDX indices and wire.TOPK_VAL values")
+    layers = None if np.ndim(shapes) == 0 else mxfp4_layer_shapes(shapes)
+    M = int(shapes) if layers is None else sum(int(np.prod(sh, dtype=np.int64)) for sh in layers)
+    i, v = indices["topk_idx"].reshape(-1), values["topk_f32"].reshape(-1)
+    if i.size != v.size or (i.size and int(i.max()) >= M):
+        raise ValueError(f"topk_to_float32: {i.size} indices and {v.size} values for {M} elements, or an index past them")
+    flat = np.zeros(M, np.float32)
+    flat[i] = v
+    if layers is None:
+        return flat
+    out, off = [], 0
+    for sh in layers:
+        n = int(np.prod(sh, dtype=np.int64))
+        out.append(flat[off : off + n].reshape(sh))
+        off += n
+    return out
+
+
 class _Bucket:
     """Owner of one flat byte buffer (1-D uint8, C-contiguous, writable)."""
 
