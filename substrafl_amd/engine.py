@@ -128,6 +128,34 @@ def check_downlink(downlink) -> None:
         raise ValueError(f"downlink must be None or 'mxfp8', not {downlink!r}")
 
 
+ROBUST_RULES = ("trimmed_mean", "median")
+
+
+def check_robust(robust, trim, downlink=None) -> None:
+    """FedAvg's ``robust`` option: None (the weighted average, as ever), ``"trimmed_mean"`` with its
+    share ``trim`` in [0, 0.5), or ``"median"``; anything else is a ``ValueError``.  ``trim``
+    with ``"median"`` or without ``robust`` is a ``TypeError``.  The robust route returns the dense
+    fp32 average: together with ``downlink`` it is a ``NotImplementedError``."""
+    if robust is not None and robust not in ROBUST_RULES:
+        raise ValueError(f"robust must be None, 'trimmed_mean' or 'median', not {robust!r}")
+    if robust != "trimmed_mean":
+        if trim is not None:
+            raise TypeError("trim is an option of robust='trimmed_mean'"
+                            + (", not of robust='median'" if robust else " (robust is not set)"))
+    elif (isinstance(trim, bool) or not isinstance(trim, (int, float, np.integer, np.floating))
+          or not 0 <= float(trim) < 0.5):
+        raise ValueError(f"robust='trimmed_mean' needs trim, a number in [0, 0.5), not {trim!r}")
+    if robust is not None and downlink is not None:
+        raise NotImplementedError(f"FedAvg engine: the robust route has no downlink={downlink!r} path "
+                                  "(it returns the dense fp32 average)")
+
+
+def robust_trim_count(rule: str, trim, K: int) -> int:
+    """``t``, the values dropped at each end of an element's K sorted client values:
+    ``floor(trim * K)`` for the trimmed mean, ``(K - 1) // 2`` for the median."""
+    return (K - 1) // 2 if rule == "median" else int(np.floor(float(trim) * K))
+
+
 def native_byte_order(rows):
     """``rows`` (lists of arrays) with every array in non-native byte order (a pickle written on
     a big-endian host) replaced by a native copy -- exact, and the byte order NumPy's ufuncs give
@@ -1006,6 +1034,95 @@ class AggregationEngine:
         out = ooc.fedavg_routed(parameters_updates, n_samples, wire)
         self.last_timing = {"out_of_core": ooc.last_timing, "staging": "out-of-core"}
         return out
+
+    # ----------------------------------------------------------------------------------
+    def fedavg_robust(self, parameters_updates: List[List[np.ndarray]], rule: str, trim: Optional[float] = None,
+                      wire: bool = False) -> List[np.ndarray]:
+        """Robust FedAvg: per element the K client values are sorted (``np.sort``'s order, NaN
+        last), the ``t`` lowest and ``t`` highest are dropped and the rest are averaged in ascending
+        order in fp32 (``include/fedagg_robust.h``).  ``rule="trimmed_mean"`` with ``trim``
+        in [0, 0.5): ``t = floor(trim * K)``; ``rule="median"``: ``t = (K - 1) // 2``.  Up to ``t``
+        clients that send NaN, Inf or a diverged update change no element's result beyond which
+        values are kept.  The rule is **unweighted**: every client has one vote, so no sample
+        counts are taken.  Layers all fp32 or all ``wire.BF16`` (widened exactly); the result is fp32.
+
+        Single GPU, in core, rows layout: the K rows are staged from the host through the session,
+        one ``fedagg_robust_mean`` call reduces them and the L fp32 layers come home (``wire``: as
+        :class:`wire.BucketArray` layers of one bucket).  The device hand-off is not wired: with it
+        enabled the rows are still staged from the host arrays, and ``last_timing["staging"]`` says so.
+
+        Refused before any device work (``NotImplementedError``, each naming the robust route):
+        MXFP8, MXFP4 or top-k updates, fp16, fp64, integer or mixed-dtype layers, more than
+        ``FEDAGG_ROBUST_MAX_K`` clients and buckets beyond the in-core budget."""
+        from . import _native_robust
+
+        if rule is None:
+            raise ValueError("robust must be 'trimmed_mean' or 'median' on the robust route, not None")
+        check_robust(rule, trim)
+        K = len(parameters_updates)
+        if K == 0 or len(parameters_updates[0]) == 0:
+            return []
+        for has, name in ((has_topk, "top-k"), (has_mxfp4, "MXFP4"), (has_mxfp8, "MXFP8")):
+            if any(has(pu) for pu in parameters_updates):
+                raise NotImplementedError(f"FedAvg engine: the robust route has no {name} path (it takes dense "
+                                          "fp32 or wire.BF16 updates)")
+        parameters_updates = native_byte_order(parameters_updates)
+        dts = {np.asarray(a).dtype for pu in parameters_updates for a in pu}
+        if len(dts) != 1 or next(iter(dts)) not in (np.dtype(np.float32), BF16):
+            raise NotImplementedError("FedAvg engine: the robust route takes layers that are all fp32 or all "
+                                      f"wire.BF16, not {sorted(str(d) for d in dts)}")
+        if K > _native_robust.MAX_K:
+            raise NotImplementedError(f"FedAvg engine: the robust route takes up to {_native_robust.MAX_K} clients "
+                                      f"(got {K}): every value of an element is held in registers at once")
+        (R,) = dts
+        layout = BucketLayout(range(len(parameters_updates[0])), [np.shape(a) for a in parameters_updates[0]], R)
+        need = K * layout.ld * R.itemsize + 4 * layout.ld  # the rows and the fp32 result
+        if self.max_bucket_bytes is not None and need > int(self.max_bucket_bytes):
+            self._robust_past_budget(need)
+        return self._fedavg_robust(parameters_updates, robust_trim_count(rule, trim, K), wire, layout, need)
+
+    @staticmethod
+    def _robust_past_budget(need: int):
+        raise NotImplementedError(f"FedAvg engine: the out-of-core route has no robust path ({need} bytes do "
+                                  "not fit the bucket budget)")
+
+    @serialized
+    def _fedavg_robust(self, parameters_updates, t: int, wire: bool, layout: BucketLayout, need: int):
+        from . import _native_robust
+
+        t_start = time.perf_counter()
+        K, R = len(parameters_updates), layout.dtype
+        if self.max_bucket_bytes is None:
+            from .multi_device import HBM_HEADROOM
+
+            slots = (self._B_BUCKET, self._B_OUT)
+            if need > int((runtime.device_memory(self._index())[0] + self.session().held_bytes(slots)) * HBM_HEADROOM):
+                self._robust_past_budget(need)
+        s = self.session()
+        self.last_timing = tm = {}
+        self._prestaged = {}
+
+        t0 = time.perf_counter()
+        ld_bytes = layout.ld * R.itemsize
+        d_rows = s.buffer(self._B_BUCKET, K * ld_bytes)
+        self._stage_rows(s, [list(pu) for pu in parameters_updates], layout, d_rows)
+        tm["staging"] = "robust-host-rows (hand-off not wired)" if handoff.enabled() else "robust-host-rows"
+        tm["prestaged"] = False
+        tm["layout"] = "rows"
+        tm["trimmed_each_end"] = t
+        tm["stage_s"] = time.perf_counter() - t0
+        t1 = time.perf_counter()
+        d_out = s.buffer(self._B_OUT, layout.ld * 4)
+        _native_robust.mean([d_rows + k * ld_bytes for k in range(K)],
+                            _native.FEDAGG_BF16 if R == BF16 else _native.FEDAGG_F32, t, layout.M, d_out, s.stream)
+        out = runtime.reusable_host_array(layout.M, np.dtype(np.float32), "fedavg-robust")
+        if layout.M:
+            s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+        tm.update({f"native_{k}": v for k, v in s.timing().items()})
+        tm["total_s"] = time.perf_counter() - t_start
+        return [results[li] for li in range(len(results))]
 
     # ----------------------------------------------------------------------------------
     def fedavg_topk(self, parameters_updates: List[List[np.ndarray]], n_samples: Sequence[int],

@@ -52,7 +52,7 @@ from typing import Optional
 import numpy as np
 
 from . import handoff
-from .engine import Devices, check_downlink, engine_for
+from .engine import Devices, check_downlink, check_robust, engine_for
 from .strategies.fed_avg import check_same_shapes, weighted_average
 from .strategies.fed_pca import orthonormal_layers
 from .strategies.scaffold import Scaffold as _MirrorScaffold
@@ -82,7 +82,7 @@ def _check_solve(solve: str) -> str:
 
 
 def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host",
-               downlink: Optional[str] = None):
+               downlink: Optional[str] = None, robust: Optional[str] = None, trim: Optional[float] = None):
     """A subclass of the reference strategy class ``strategy_cls`` (``FedAvg``, ``Scaffold``,
     ``FedPCA``, ``NewtonRaphson`` or a subclass of one of them) whose aggregation methods run on the
     engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
@@ -96,9 +96,14 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
     overrides it, read when the aggregation runs.  ``downlink`` is FedAvg's alone (a ``TypeError``
     for the others, any string but ``"mxfp8"`` a ``ValueError``): ``"mxfp8"`` sends the average of
     clients on the MXFP8 or MXFP4 wire back encoded to MXFP8
-    (:meth:`engine.AggregationEngine.fedavg_mxfp8`); None, the default, changes nothing."""
+    (:meth:`engine.AggregationEngine.fedavg_mxfp8`); None, the default, changes nothing.  ``robust``
+    and ``trim`` are FedAvg's alone too (a ``TypeError`` for the others): ``robust="trimmed_mean"`` with
+    ``trim`` in [0, 0.5), or ``robust="median"``, replaces the weighted average by the unweighted
+    coordinate-wise trimmed mean or median (:meth:`engine.AggregationEngine.fedavg_robust`); any other
+    string, or a bad ``trim``, is a ``ValueError``, ``trim`` without the trimmed mean a ``TypeError``."""
     _check_solve(solve)
     check_downlink(downlink)
+    check_robust(robust, trim, downlink)
     if qr not in ("host", "device"):
         raise ValueError(f"qr must be 'host' or 'device', not {qr!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
@@ -112,6 +117,9 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
     if downlink is not None and (issubclass(strategy_cls, (strategies.Scaffold, strategies.FedPCA))
                                  or not issubclass(strategy_cls, strategies.FedAvg)):
         raise TypeError(f"downlink is an option of FedAvg, not of {strategy_cls.__name__}")
+    if robust is not None and (issubclass(strategy_cls, (strategies.Scaffold, strategies.FedPCA))
+                               or not issubclass(strategy_cls, strategies.FedAvg)):
+        raise TypeError(f"robust is an option of FedAvg, not of {strategy_cls.__name__}")
     ns = {"__doc__": f"{strategy_cls.__name__} with its aggregation on MI355X (substrafl_amd.integration).",
           "__init__": __init__,
           "_fedagg_device": device,
@@ -155,10 +163,13 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
         def avg_shared_states(self, shared_states):
             """fed_avg.py:176-224 on the engine."""
             out = weighted_average(shared_states, "FedAvgSharedState", self._fedagg_device, wire=False,
-                                   empty_error=empty, downlink=self._fedagg_downlink)
+                                   empty_error=empty, downlink=self._fedagg_downlink,
+                                   robust=getattr(self, "_fedagg_robust", None), trim=getattr(self, "_fedagg_trim", None))
             return averaged_cls(avg_parameters_update=out)
 
         ns["_fedagg_downlink"] = downlink
+        if robust is not None:  # recorded only when given: every other class stays attribute for attribute what it is
+            ns["_fedagg_robust"], ns["_fedagg_trim"] = robust, trim
         ns["avg_shared_states"] = remote(avg_shared_states)
         ns["_aggregation_methods"] = {"avg_shared_states": "fedavg"}
     elif getattr(strategies, "NewtonRaphson", None) is not None and issubclass(strategy_cls, strategies.NewtonRaphson):

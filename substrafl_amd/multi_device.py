@@ -373,6 +373,12 @@ class MultiDeviceEngine:
             return self.fedavg(parameters_updates, n_samples, wire)
         return self._fedavg_bf16(parameters_updates, n_samples, wire)
 
+    def fedavg_robust(self, parameters_updates, rule, trim=None, wire: bool = False):
+        """Robust FedAvg (:meth:`engine.AggregationEngine.fedavg_robust`) runs on one GPU, in core:
+        a ``NotImplementedError`` here, before any device work."""
+        raise NotImplementedError("MultiDeviceEngine (several devices, or out of core): no robust route "
+                                  f"(robust={rule!r} runs on one GPU, in core: FedAvg(..., device=<one index>))")
+
     @serialized
     def _fedavg_bf16(self, parameters_updates, n_samples, wire: bool):
         return self._fedavg_ranges(native_byte_order(parameters_updates), n_samples, wire, BF16,

@@ -11,7 +11,7 @@ from typing import List, Optional
 
 import numpy as np
 
-from ..engine import Devices, check_downlink, engine_for
+from ..engine import Devices, check_downlink, check_robust, engine_for
 from ..exceptions import EmptySharedStatesError
 from ..remote import remote
 from ..schemas import FedAvgAveragedState, FedAvgSharedState, StrategyName
@@ -38,14 +38,28 @@ class FedAvg(Strategy):
     ``downlink="mxfp8"`` (None, the default, changes nothing; any other string is a ``ValueError``):
     the average of clients on the MXFP8 or MXFP4 wire goes back to them encoded to MXFP8, 1.03 bytes
     per parameter instead of 4 (:meth:`engine.AggregationEngine.fedavg_mxfp8`); their
-    ``weight_manager.increment_parameters`` decodes it on the device.  It carries no residual."""
+    ``weight_manager.increment_parameters`` decodes it on the device.  It carries no residual.
 
-    def __init__(self, algo, metric_functions=None, device: Devices = None, downlink: Optional[str] = None):
+    ``robust="trimmed_mean"`` with ``trim`` in [0, 0.5), or ``robust="median"`` (None, the default,
+    changes nothing; any other string is a ``ValueError``): the coordinate-wise trimmed mean, per
+    element the ``floor(trim * K)`` lowest and highest of the K client values dropped and the rest
+    averaged, or the median as its limit case (:meth:`engine.AggregationEngine.fedavg_robust`).  A
+    client that sends NaN, Inf or a diverged update then no longer reaches the average.  The rule is
+    **unweighted**: ``n_samples`` is validated as ever but every client has one vote.  ``trim`` is
+    required for the trimmed mean (a bool, a non-number or a value outside [0, 0.5) is a
+    ``ValueError``) and a ``TypeError`` with the median or without ``robust``.  Clients are untouched:
+    the average comes back dense fp32."""
+
+    def __init__(self, algo, metric_functions=None, device: Devices = None, downlink: Optional[str] = None,
+                 robust: Optional[str] = None, trim: Optional[float] = None):
         check_downlink(downlink)
-        extra = {k: v for k, v in (("device", device), ("downlink", downlink)) if v is not None}
+        check_robust(robust, trim, downlink)
+        extra = {k: v for k, v in (("device", device), ("downlink", downlink), ("robust", robust), ("trim", trim))
+                 if v is not None}
         super().__init__(algo=algo, metric_functions=metric_functions, **extra)  # recorded only when given
         self._device = device
         self._downlink = downlink
+        self._robust, self._trim = robust, trim
         self._local_states = None
         self._shared_states = None
 
@@ -64,17 +78,21 @@ class FedAvg(Strategy):
             ValueError: a layer's shape differs between clients (``np.sum``, fed_avg.py:222).
             pydantic.ValidationError: a 0-d layer (its average is a scalar, schemas.py:29).
         """
-        averaged_states = weighted_average(shared_states, "FedAvgSharedState", self._device, downlink=self._downlink)
+        averaged_states = weighted_average(shared_states, "FedAvgSharedState", self._device, downlink=self._downlink,
+                                           robust=self._robust, trim=self._trim)
         return FedAvgAveragedState(avg_parameters_update=averaged_states)
 
 
 def weighted_average(shared_states, state_name: str, device: Devices = None, wire: bool = True,
-                     empty_error=EmptySharedStatesError, downlink: Optional[str] = None) -> List[np.ndarray]:
+                     empty_error=EmptySharedStatesError, downlink: Optional[str] = None,
+                     robust: Optional[str] = None, trim: Optional[float] = None) -> List[np.ndarray]:
     """fed_avg.py:207-222 (also fed_pca.py:244-257): validation on the host, the weighted sum
     of every layer on the GPU.  ``wire``: layers in the flat wire format (this package's own
     schemas); False: plain NumPy arrays (the reference's schemas, :mod:`substrafl_amd.integration`).
     ``empty_error``: the exception class raised for an empty list (the reference's own there).
-    ``downlink``: FedAvg's option, passed to the engine's ``fedavg_routed`` when set."""
+    ``downlink``: FedAvg's option, passed to the engine's ``fedavg_routed`` when set.  ``robust`` /
+    ``trim``: FedAvg's options; when ``robust`` is set the engine's ``fedavg_robust`` reduces the layers
+    by the unweighted trimmed mean or median instead (``n_samples`` is validated but not used)."""
     if len(shared_states) == 0:
         raise empty_error(
             "Your shared_states is empty. Please ensure that "
@@ -95,6 +113,9 @@ def weighted_average(shared_states, state_name: str, device: Devices = None, wir
     if not any(has_topk(u) for u in updates):  # top-k rows differ in length: the engine compares their shape tables
         check_same_shapes(updates)
     engine = engine_for(device)
+    if robust is not None:
+        check_robust(robust, trim, downlink)
+        return engine.fedavg_robust(updates, robust, trim, wire=wire)
     # substrafl_amd's own schemas already need this package to unpickle: the flat wire format.
     # fedavg_routed where the engine has it: fedavg, plus wire.BF16 states on the multi-GPU and
     # out-of-core routes, which fedavg itself refuses
