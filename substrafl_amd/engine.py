@@ -128,26 +128,100 @@ def check_downlink(downlink) -> None:
         raise ValueError(f"downlink must be None or 'mxfp8', not {downlink!r}")
 
 
-ROBUST_RULES = ("trimmed_mean", "median")
+ROBUST_RULES = ("trimmed_mean", "median", "krum", "multi_krum")
+KRUM_RULES = ("krum", "multi_krum")
 
 
-def check_robust(robust, trim, downlink=None) -> None:
+def _is_int(v) -> bool:
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def check_robust(robust, trim, downlink=None, byzantine=None, select=None) -> None:
     """FedAvg's ``robust`` option: None (the weighted average, as ever), ``"trimmed_mean"`` with its
-    share ``trim`` in [0, 0.5), or ``"median"``; anything else is a ``ValueError``.  ``trim``
-    with ``"median"`` or without ``robust`` is a ``TypeError``.  The robust route returns the dense
-    fp32 average: together with ``downlink`` it is a ``NotImplementedError``."""
+    share ``trim`` in [0, 0.5), ``"median"``, or ``"krum"`` / ``"multi_krum"`` with ``byzantine``, the
+    number f >= 0 of clients the rule is to withstand; anything else is a ``ValueError``.
+    ``trim`` with any rule but the trimmed mean, ``byzantine`` with any rule but the two Krum rules and
+    ``select`` (the clients multi-Krum averages, an int >= 1) with any rule but ``"multi_krum"`` are a
+    ``TypeError``, as each is without ``robust``.  What depends on the number of clients
+    (``K >= 2 f + 3``, ``select <= K - f``) is checked where K is known (:func:`krum_counts`).  The
+    robust route returns the dense fp32 average: together with ``downlink`` it is a
+    ``NotImplementedError``."""
     if robust is not None and robust not in ROBUST_RULES:
-        raise ValueError(f"robust must be None, 'trimmed_mean' or 'median', not {robust!r}")
+        raise ValueError(f"robust must be None, 'trimmed_mean' or 'median', or 'krum' or 'multi_krum', not {robust!r}")
     if robust != "trimmed_mean":
         if trim is not None:
             raise TypeError("trim is an option of robust='trimmed_mean'"
-                            + (", not of robust='median'" if robust else " (robust is not set)"))
+                            + (f", not of robust={robust!r}" if robust else " (robust is not set)"))
     elif (isinstance(trim, bool) or not isinstance(trim, (int, float, np.integer, np.floating))
           or not 0 <= float(trim) < 0.5):
         raise ValueError(f"robust='trimmed_mean' needs trim, a number in [0, 0.5), not {trim!r}")
+    if robust not in KRUM_RULES:
+        if byzantine is not None:
+            raise TypeError("byzantine is an option of robust='krum' and robust='multi_krum'"
+                            + (f", not of robust={robust!r}" if robust else " (robust is not set)"))
+    elif not _is_int(byzantine) or byzantine < 0:
+        raise ValueError(f"robust={robust!r} needs byzantine, an int >= 0, not {byzantine!r}")
+    if robust != "multi_krum":
+        if select is not None:
+            raise TypeError("select is an option of robust='multi_krum'"
+                            + (f", not of robust={robust!r}" if robust else " (robust is not set)"))
+    elif select is not None and (not _is_int(select) or select < 1):
+        raise ValueError(f"robust='multi_krum' takes select, an int >= 1, not {select!r}")
     if robust is not None and downlink is not None:
         raise NotImplementedError(f"FedAvg engine: the robust route has no downlink={downlink!r} path "
                                   "(it returns the dense fp32 average)")
+
+
+def krum_counts(rule: str, byzantine: int, select, K: int) -> Tuple[int, int]:
+    """``(f, m)`` for K clients: Krum needs ``K >= 2 f + 3``; ``"krum"`` selects m = 1 client,
+    ``"multi_krum"`` ``select`` of them, by default and at most ``K - f``.  A ``ValueError`` names both
+    numbers."""
+    f = int(byzantine)
+    if K < 2 * f + 3:
+        raise ValueError(f"robust={rule!r} with byzantine={f} needs at least 2 f + 3 = {2 * f + 3} clients, not {K}")
+    if rule == "krum":
+        return f, 1
+    m = K - f if select is None else int(select)
+    if not 1 <= m <= K - f:
+        raise ValueError(f"robust='multi_krum' takes select in [1, K - f] = [1, {K - f}] (K={K}, byzantine={f}), "
+                         f"not {m}")
+    return f, m
+
+
+def krum_scores(G, byzantine: int) -> np.ndarray:
+    """Krum's score of every client from the Gram matrix ``G`` of the K updates, in fp64:
+    ``d_ij = max(G_ii + G_jj - 2 G_ij, 0)``, a client whose ``G_ii`` is not finite at distance +inf
+    from everyone, and ``score_i`` the sum of the ``K - f - 2`` smallest ``d_ij``, ``j != i``."""
+    G = np.asarray(G, np.float64)
+    K, f = G.shape[0], int(byzantine)
+    if G.ndim != 2 or G.shape[1] != K:
+        raise ValueError(f"G must be a square matrix, not {G.shape}")
+    n = K - f - 2
+    if f < 0 or n < 1:
+        raise ValueError(f"Krum with byzantine={f} needs at least {max(f, 0) + 3} clients, not {K}")
+    g = np.diagonal(G)
+    with np.errstate(all="ignore"):
+        d = np.maximum(g[:, None] + g[None, :] - 2.0 * G, 0.0)
+    bad = ~np.isfinite(g)
+    d[bad, :] = np.inf
+    d[:, bad] = np.inf
+    np.fill_diagonal(d, np.inf)  # j != i: K - 1 >= n others remain, and an inf among the n smallest is an inf score anyway
+    return np.sort(d, axis=1)[:, :n].sum(axis=1)
+
+
+def krum_select(G, byzantine: int, select: int) -> np.ndarray:
+    """The ``select`` clients with the lowest Krum scores (:func:`krum_scores`), ties going to the
+    lower index, as ascending client indices.  Pure NumPy, no device work.  A selected score that is
+    not finite means that more than ``byzantine`` clients sent non-finite updates: a ``ValueError``."""
+    scores = krum_scores(G, byzantine)
+    m = int(select)
+    if not 1 <= m <= scores.size:
+        raise ValueError(f"select must be in [1, {scores.size}], not {select!r}")
+    chosen = np.argsort(scores, kind="stable")[:m]
+    if not np.isfinite(scores[chosen]).all():
+        raise ValueError(f"Krum: more than byzantine={int(byzantine)} clients sent non-finite updates "
+                         f"({int((~np.isfinite(np.diagonal(np.asarray(G)))).sum())} did)")
+    return np.sort(chosen)
 
 
 def robust_trim_count(rule: str, trim, K: int) -> int:
@@ -1037,7 +1111,8 @@ class AggregationEngine:
 
     # ----------------------------------------------------------------------------------
     def fedavg_robust(self, parameters_updates: List[List[np.ndarray]], rule: str, trim: Optional[float] = None,
-                      wire: bool = False) -> List[np.ndarray]:
+                      wire: bool = False, byzantine: Optional[int] = None,
+                      select: Optional[int] = None) -> List[np.ndarray]:
         """Robust FedAvg: per element the K client values are sorted (``np.sort``'s order, NaN
         last), the ``t`` lowest and ``t`` highest are dropped and the rest are averaged in ascending
         order in fp32 (``include/fedagg_robust.h``).  ``rule="trimmed_mean"`` with ``trim``
@@ -1051,14 +1126,25 @@ class AggregationEngine:
         :class:`wire.BucketArray` layers of one bucket).  The device hand-off is not wired: with it
         enabled the rows are still staged from the host arrays, and ``last_timing["staging"]`` says so.
 
+        ``rule="krum"`` / ``"multi_krum"`` with ``byzantine=f`` (Blanchard et al. 2017; ``K >= 2 f + 3``)
+        select whole clients instead, by their pairwise distances: a client that is an inlier in every
+        coordinate but wrong as a vector passes the coordinate-wise rules and not these.  The rows
+        are staged once, ``fedagg_krum_gram`` forms their K x K fp64 Gram matrix on the matrix units
+        (``include/fedagg_krum.h``), the matrix comes home and :func:`krum_select` picks 1 client, or
+        ``select`` of them (default ``K - f``); then ``fedagg_fedavg_f32`` / ``_bf16`` averages the
+        selected rows where they lie, in ascending client order with the weights
+        ``fedavg_weights([1] * m, kind)``: bit for bit the reference's FedAvg of the selected clients
+        with equal sample counts, and for ``"krum"`` the chosen client's update itself.
+        ``last_timing`` records ``krum_selected``, ``krum_scores`` and the Gram, select and average times.
+
         Refused before any device work (``NotImplementedError``, each naming the robust route):
         MXFP8, MXFP4 or top-k updates, fp16, fp64, integer or mixed-dtype layers, more than
         ``FEDAGG_ROBUST_MAX_K`` clients and buckets beyond the in-core budget."""
-        from . import _native_robust
+        from . import _native_krum, _native_robust
 
         if rule is None:
             raise ValueError("robust must be 'trimmed_mean' or 'median' on the robust route, not None")
-        check_robust(rule, trim)
+        check_robust(rule, trim, None, byzantine, select)
         K = len(parameters_updates)
         if K == 0 or len(parameters_updates[0]) == 0:
             return []
@@ -1071,14 +1157,23 @@ class AggregationEngine:
         if len(dts) != 1 or next(iter(dts)) not in (np.dtype(np.float32), BF16):
             raise NotImplementedError("FedAvg engine: the robust route takes layers that are all fp32 or all "
                                       f"wire.BF16, not {sorted(str(d) for d in dts)}")
-        if K > _native_robust.MAX_K:
+        krum = rule in KRUM_RULES
+        if krum and K > _native_krum.MAX_K:
+            raise NotImplementedError(f"FedAvg engine: the robust route takes up to {_native_krum.MAX_K} clients "
+                                      f"(got {K}): the Gram kernel holds 8 blocks of 16 clients")
+        if not krum and K > _native_robust.MAX_K:
             raise NotImplementedError(f"FedAvg engine: the robust route takes up to {_native_robust.MAX_K} clients "
                                       f"(got {K}): every value of an element is held in registers at once")
+        counts = krum_counts(rule, byzantine, select, K) if krum else None
         (R,) = dts
         layout = BucketLayout(range(len(parameters_updates[0])), [np.shape(a) for a in parameters_updates[0]], R)
         need = K * layout.ld * R.itemsize + 4 * layout.ld  # the rows and the fp32 result
+        if krum:
+            need += 8 * K * K  # G; the partial triangles (tens of MB at most) are added once the library says how many
         if self.max_bucket_bytes is not None and need > int(self.max_bucket_bytes):
             self._robust_past_budget(need)
+        if krum:
+            return self._fedavg_krum(parameters_updates, counts, wire, layout, need)
         return self._fedavg_robust(parameters_updates, robust_trim_count(rule, trim, K), wire, layout, need)
 
     @staticmethod
@@ -1118,6 +1213,66 @@ class AggregationEngine:
         out = runtime.reusable_host_array(layout.M, np.dtype(np.float32), "fedavg-robust")
         if layout.M:
             s.fetch(d_out, out)  # stream-ordered after the kernels; returns when the data is home
+        tm["kernel_fetch_s"] = time.perf_counter() - t1
+        results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
+        tm.update({f"native_{k}": v for k, v in s.timing().items()})
+        tm["total_s"] = time.perf_counter() - t_start
+        return [results[li] for li in range(len(results))]
+
+    @serialized
+    def _fedavg_krum(self, parameters_updates, counts: Tuple[int, int], wire: bool, layout: BucketLayout, need: int):
+        from . import _native_krum
+
+        t_start = time.perf_counter()
+        (f, m), K, R = counts, len(parameters_updates), layout.dtype
+        kind = kind_of(R)
+        ws_gram = _native_krum.ws_bytes(K, layout.M)
+        ws_bytes = max(ws_gram, int(_native.load().fedagg_pairwise_ws_bytes(m, layout.pairwise_idx.size, 8)))
+        need += ws_bytes
+        if self.max_bucket_bytes is not None and need > int(self.max_bucket_bytes):
+            self._robust_past_budget(need)
+        if self.max_bucket_bytes is None:
+            from .multi_device import HBM_HEADROOM
+
+            slots = (self._B_BUCKET, self._B_OUT, self._B_WS, self._B_TMP)
+            if need > int((runtime.device_memory(self._index())[0] + self.session().held_bytes(slots)) * HBM_HEADROOM):
+                self._robust_past_budget(need)
+        s = self.session()
+        self.last_timing = tm = {}
+        self._prestaged = {}
+
+        t0 = time.perf_counter()
+        ld_bytes = layout.ld * R.itemsize
+        d_rows = s.buffer(self._B_BUCKET, K * ld_bytes)
+        self._stage_rows(s, [list(pu) for pu in parameters_updates], layout, d_rows)  # once: both kernels read them here
+        tm["staging"] = "robust-host-rows (hand-off not wired)" if handoff.enabled() else "robust-host-rows"
+        tm["prestaged"] = False
+        tm["layout"] = "rows"
+        tm["stage_s"] = time.perf_counter() - t0
+        t1 = time.perf_counter()
+        ptrs = [d_rows + k * ld_bytes for k in range(K)]
+        d_ws = s.buffer(self._B_WS, ws_bytes)
+        d_G = s.buffer(self._B_TMP, 8 * K * K)
+        _native_krum.gram(ptrs, _native.FEDAGG_BF16 if R == BF16 else _native.FEDAGG_F32, layout.M, d_ws, ws_gram, d_G,
+                          s.stream)
+        G = np.empty((K, K), np.float64)
+        s.fetch(d_G, G)  # stream-ordered after the two kernels; at most 128 KB
+        tm["krum_gram_s"] = time.perf_counter() - t1
+        t2 = time.perf_counter()
+        scores = krum_scores(G, f)
+        chosen = krum_select(G, f, m)
+        tm["krum_byzantine"] = f
+        tm["krum_selected"] = [int(k) for k in chosen]
+        tm["krum_scores"] = [float(v) for v in scores]
+        tm["krum_select_s"] = time.perf_counter() - t2
+        t3 = time.perf_counter()
+        d_out = s.buffer(self._B_OUT, layout.ld * 4)
+        out = runtime.reusable_host_array(layout.M, np.dtype(np.float32), "fedavg-krum")
+        if layout.M:
+            FedAvgPlan(kind, [ptrs[k] for k in chosen], fedavg_weights([1] * m, kind), layout.M, d_out,
+                       layout.pairwise_idx, d_ws).launch(s.stream)
+            s.fetch(d_out, out)
+        tm["krum_average_s"] = time.perf_counter() - t3
         tm["kernel_fetch_s"] = time.perf_counter() - t1
         results: Dict[int, np.ndarray] = dict(layout.unpack(out, wire))
         tm.update({f"native_{k}": v for k, v in s.timing().items()})

@@ -82,7 +82,8 @@ def _check_solve(solve: str) -> str:
 
 
 def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: str = "host",
-               downlink: Optional[str] = None, robust: Optional[str] = None, trim: Optional[float] = None):
+               downlink: Optional[str] = None, robust: Optional[str] = None, trim: Optional[float] = None,
+               byzantine: Optional[int] = None, select: Optional[int] = None):
     """A subclass of the reference strategy class ``strategy_cls`` (``FedAvg``, ``Scaffold``,
     ``FedPCA``, ``NewtonRaphson`` or a subclass of one of them) whose aggregation methods run on the
     engine of ``device`` (:func:`engine.engine_for`: None = the current GPU, an index, a list, or
@@ -100,10 +101,13 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
     and ``trim`` are FedAvg's alone too (a ``TypeError`` for the others): ``robust="trimmed_mean"`` with
     ``trim`` in [0, 0.5), or ``robust="median"``, replaces the weighted average by the unweighted
     coordinate-wise trimmed mean or median (:meth:`engine.AggregationEngine.fedavg_robust`); any other
-    string, or a bad ``trim``, is a ``ValueError``, ``trim`` without the trimmed mean a ``TypeError``."""
+    string, or a bad ``trim``, is a ``ValueError``, ``trim`` without the trimmed mean a ``TypeError``.
+    ``robust="krum"`` and ``robust="multi_krum"`` with ``byzantine=f`` (and, for multi-Krum, ``select``)
+    select whole clients by their pairwise distances instead (:func:`engine.krum_select`); ``byzantine``
+    and ``select`` are checked as :func:`engine.check_robust` says."""
     _check_solve(solve)
     check_downlink(downlink)
-    check_robust(robust, trim, downlink)
+    check_robust(robust, trim, downlink, byzantine, select)
     if qr not in ("host", "device"):
         raise ValueError(f"qr must be 'host' or 'device', not {qr!r}")
     strategies, schemas, remote, exceptions = _reference_modules(strategy_cls)
@@ -164,12 +168,16 @@ def accelerate(strategy_cls, device: Devices = None, solve: str = "host", qr: st
             """fed_avg.py:176-224 on the engine."""
             out = weighted_average(shared_states, "FedAvgSharedState", self._fedagg_device, wire=False,
                                    empty_error=empty, downlink=self._fedagg_downlink,
-                                   robust=getattr(self, "_fedagg_robust", None), trim=getattr(self, "_fedagg_trim", None))
+                                   robust=getattr(self, "_fedagg_robust", None), trim=getattr(self, "_fedagg_trim", None),
+                                   byzantine=getattr(self, "_fedagg_byzantine", None),
+                                   select=getattr(self, "_fedagg_select", None))
             return averaged_cls(avg_parameters_update=out)
 
         ns["_fedagg_downlink"] = downlink
         if robust is not None:  # recorded only when given: every other class stays attribute for attribute what it is
             ns["_fedagg_robust"], ns["_fedagg_trim"] = robust, trim
+            if byzantine is not None:
+                ns["_fedagg_byzantine"], ns["_fedagg_select"] = byzantine, select
         ns["avg_shared_states"] = remote(avg_shared_states)
         ns["_aggregation_methods"] = {"avg_shared_states": "fedavg"}
     elif getattr(strategies, "NewtonRaphson", None) is not None and issubclass(strategy_cls, strategies.NewtonRaphson):

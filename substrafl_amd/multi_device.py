@@ -373,7 +373,7 @@ class MultiDeviceEngine:
             return self.fedavg(parameters_updates, n_samples, wire)
         return self._fedavg_bf16(parameters_updates, n_samples, wire)
 
-    def fedavg_robust(self, parameters_updates, rule, trim=None, wire: bool = False):
+    def fedavg_robust(self, parameters_updates, rule, trim=None, wire: bool = False, byzantine=None, select=None):
         """Robust FedAvg (:meth:`engine.AggregationEngine.fedavg_robust`) runs on one GPU, in core:
         a ``NotImplementedError`` here, before any device work."""
         raise NotImplementedError("MultiDeviceEngine (several devices, or out of core): no robust route "

@@ -48,18 +48,30 @@ class FedAvg(Strategy):
     **unweighted**: ``n_samples`` is validated as ever but every client has one vote.  ``trim`` is
     required for the trimmed mean (a bool, a non-number or a value outside [0, 0.5) is a
     ``ValueError``) and a ``TypeError`` with the median or without ``robust``.  Clients are untouched:
-    the average comes back dense fp32."""
+    the average comes back dense fp32.
+
+    ``robust="krum"`` or ``robust="multi_krum"`` with ``byzantine=f`` (Blanchard et al. 2017): whole
+    clients are selected by their pairwise distances, which catches an update that is an inlier in
+    every coordinate but wrong as a vector (sign-flipped, colluding).  Krum returns the one client
+    closest to its ``K - f - 2`` nearest neighbours, multi-Krum the unweighted average of the
+    ``select`` best (default and at most ``K - f``); ``K >= 2 f + 3`` clients are needed (a
+    ``ValueError`` when the states arrive).  ``byzantine`` is required (a bool, a non-int or a negative
+    value is a ``ValueError``) and, like ``select`` outside multi-Krum, a ``TypeError`` with any other
+    rule or without ``robust``."""
 
     def __init__(self, algo, metric_functions=None, device: Devices = None, downlink: Optional[str] = None,
-                 robust: Optional[str] = None, trim: Optional[float] = None):
+                 robust: Optional[str] = None, trim: Optional[float] = None, byzantine: Optional[int] = None,
+                 select: Optional[int] = None):
         check_downlink(downlink)
-        check_robust(robust, trim, downlink)
-        extra = {k: v for k, v in (("device", device), ("downlink", downlink), ("robust", robust), ("trim", trim))
+        check_robust(robust, trim, downlink, byzantine, select)
+        extra = {k: v for k, v in (("device", device), ("downlink", downlink), ("robust", robust), ("trim", trim),
+                                   ("byzantine", byzantine), ("select", select))
                  if v is not None}
         super().__init__(algo=algo, metric_functions=metric_functions, **extra)  # recorded only when given
         self._device = device
         self._downlink = downlink
         self._robust, self._trim = robust, trim
+        self._byzantine, self._select = byzantine, select
         self._local_states = None
         self._shared_states = None
 
@@ -79,20 +91,23 @@ class FedAvg(Strategy):
             pydantic.ValidationError: a 0-d layer (its average is a scalar, schemas.py:29).
         """
         averaged_states = weighted_average(shared_states, "FedAvgSharedState", self._device, downlink=self._downlink,
-                                           robust=self._robust, trim=self._trim)
+                                           robust=self._robust, trim=self._trim, byzantine=self._byzantine,
+                                           select=self._select)
         return FedAvgAveragedState(avg_parameters_update=averaged_states)
 
 
 def weighted_average(shared_states, state_name: str, device: Devices = None, wire: bool = True,
                      empty_error=EmptySharedStatesError, downlink: Optional[str] = None,
-                     robust: Optional[str] = None, trim: Optional[float] = None) -> List[np.ndarray]:
+                     robust: Optional[str] = None, trim: Optional[float] = None, byzantine: Optional[int] = None,
+                     select: Optional[int] = None) -> List[np.ndarray]:
     """fed_avg.py:207-222 (also fed_pca.py:244-257): validation on the host, the weighted sum
     of every layer on the GPU.  ``wire``: layers in the flat wire format (this package's own
     schemas); False: plain NumPy arrays (the reference's schemas, :mod:`substrafl_amd.integration`).
     ``empty_error``: the exception class raised for an empty list (the reference's own there).
     ``downlink``: FedAvg's option, passed to the engine's ``fedavg_routed`` when set.  ``robust`` /
     ``trim``: FedAvg's options; when ``robust`` is set the engine's ``fedavg_robust`` reduces the layers
-    by the unweighted trimmed mean or median instead (``n_samples`` is validated but not used)."""
+    by the unweighted trimmed mean or median instead (``n_samples`` is validated but not used);
+    ``byzantine`` / ``select``: the options of its rules ``"krum"`` and ``"multi_krum"``."""
     if len(shared_states) == 0:
         raise empty_error(
             "Your shared_states is empty. Please ensure that "
@@ -114,8 +129,10 @@ def weighted_average(shared_states, state_name: str, device: Devices = None, wir
         check_same_shapes(updates)
     engine = engine_for(device)
     if robust is not None:
-        check_robust(robust, trim, downlink)
-        return engine.fedavg_robust(updates, robust, trim, wire=wire)
+        check_robust(robust, trim, downlink, byzantine, select)
+        if byzantine is None:
+            return engine.fedavg_robust(updates, robust, trim, wire=wire)
+        return engine.fedavg_robust(updates, robust, trim, wire=wire, byzantine=byzantine, select=select)
     # substrafl_amd's own schemas already need this package to unpickle: the flat wire format.
     # fedavg_routed where the engine has it: fedavg, plus wire.BF16 states on the multi-GPU and
     # out-of-core routes, which fedavg itself refuses
